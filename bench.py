@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the VO per-frame hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--chains B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--chains B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: render the frames, bootstrap,
+warm up, time the K steps, write the outputs (--dump-outputs) and print the result line.
+--full adds every secondary leg listed below ("--full only"); the --no-* options trim them.
 
 Workload (config C2, "KITTI seq00 1241x376 grayscale, full detect->KLT->PnP-RANSAC per-frame
 loop"): a seeded synthetic 1241x376 sequence of KITTI seq00's length (4541 frames, K of
@@ -21,6 +25,11 @@ Extra JSON fields:
   roofline     -- the dominant stage, timed with HIP events recorded on the engine's
                   stream around its launches inside the timed region; achieved =
                   algorithmic bytes (DESIGN.md "Kernels") / mean stage time
+--full only:
+  headline_vs_reference -- the headline chains that coincide with shards of the reference's
+                  256-shard cut, pose by pose (after the clock)
+  single_chain -- one chain in the drop-in class's mode (host sync per frame), plain and graph
+  c3_sift_match, c5_sift_match, c5_hd1080, roofline_matcher -- the C3 / C5 configurations
   cpu_baseline -- the CPU restatement (oracle/, OpenCV-4.6 semantics, 1 core) timed per
                   frame on this host over a bounded sample (rank 0, N=1 only)
   cpu_baseline_allcores -- the same restatement on up to 16 chains at once, one process
@@ -30,6 +39,10 @@ Extra JSON fields:
                   included: frames/s = 4541 / wall, per-shard identity with the reference
                   class's runs on the same shard boundaries, stitched ATE (sequence_leg);
                   seq00_frames_per_s repeats its frames/s at the top level
+
+--dump-outputs DIR writes what the last timed step left a caller of the stepped engines, as
+DIR/<name>.npy (see dump_outputs); the frames are a function of the arguments alone, so two
+builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -70,6 +83,11 @@ def parse():
                          "(latency-bound stages of one group overlap the others' kernels)")
     ap.add_argument("--preset", default="kitti")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: comparison with the reference shards, whole-sequence "
+                         "job and rank slices, single chain, CPU baselines + ATE, C3 / C5 configurations")
     ap.add_argument("--cpu-frames", type=int, default=100, help="CPU-baseline sample length")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=16, help="chains (processes) in the all-cores CPU leg (1: skip)")
@@ -614,6 +632,50 @@ class Headline:
                                    cat("nL"), cat("nC"), cat("status"), max_diffs=max_diffs)
 
 
+DUMP_BYTES = 60 * 1000 * 1000    # --dump-outputs writes less than this in all
+DUMP_POSES = 64                  # newest pose slots kept per chain
+DUMP_ROWS = 1024                 # leading rows kept of every per-chain point list
+# (file, state tensor, its per-chain count): the lists export_chain hands a caller
+DUMP_LISTS = (("landmarks", "lm_X", "nL"), ("keypoints", "lm_kp", "nL"), ("cand", "c_kp", "nC"),
+              ("cand_first", "c_first", "nC"), ("cand_tau", "c_tau", "nC"),
+              ("inliers", "inl_kp", "nInl"), ("outliers", "outl_kp", "nOutl"))
+DUMP_COUNTS = ("status", "nF", "nL", "nC", "nInl", "nOutl")
+
+
+def dump_outputs(path, engines, poses):
+    """Write the state the last timed step left, as a caller reads it (Engine.export_chain), to
+    path/<name>.npy; chains in job order (this rank's for everything but the gathered poses).
+      poses    f64 [chains of all ranks, P, 13]  the newest P <= DUMP_POSES pose slots (9 R, 3 t_CW,
+                                                 valid flag), the last one written by the last step
+      num_pts  f32 [B, P]                        landmark count logged with each of those poses
+      status, nF, nL, nC, nInl, nOutl  f64 [B]   chain status and list lengths
+      landmarks / keypoints / cand / cand_first / cand_tau / inliers / outliers  f32 [B, rows, ...]
+                                                 the leading rows of every list (a fixed sample when
+                                                 a list is longer); rows past the list's length are 0
+    Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    cat = lambda k: torch.cat([e.t[k] for e in engines])
+    B = sum(e.B for e in engines)
+    hi = max(1, int(poses[:, :, 12].sum(1).max().item()))
+    lo = max(0, hi - DUMP_POSES)
+    out = {"poses": poses[:, lo:hi].cpu().numpy().astype(np.float64),
+           "num_pts": cat("num_pts")[:, lo:hi].cpu().numpy().astype(np.float32)}
+    counts = {k: cat(k).to(torch.int64) for k in DUMP_COUNTS}
+    for k in DUMP_COUNTS:
+        out[k] = counts[k].cpu().numpy().astype(np.float64)
+    row_bytes = sum(4 * int(np.prod(engines[0].t[k].shape[2:])) for _, k, _ in DUMP_LISTS)
+    left = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    rows = int(max(1, min(DUMP_ROWS, left // (row_bytes * B))))
+    for name, k, cnt in DUMP_LISTS:
+        a = cat(k)[:, :rows].to(torch.float32)
+        live = torch.arange(a.shape[1], device=a.device)[None, :] < counts[cnt][:, None]
+        live = live.reshape(live.shape + (1,) * (a.dim() - 2))
+        out[name] = torch.where(live, a, torch.zeros_like(a)).cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def main():
     args = parse()
     if args.hw_queues:
@@ -683,7 +745,7 @@ def main():
     n_ok_all = n_ok
     # the chains that coincide with shards of the reference's 256-shard cut, pose by pose
     # (VERDICT r4 item 1): after the clock, never part of the timed region
-    vs_ref = hl.vs_reference() if args.preset == "kitti" and args.seed == 1 else None
+    vs_ref = hl.vs_reference() if args.full and args.preset == "kitti" and args.seed == 1 else None
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -716,8 +778,12 @@ def main():
     torch.cuda.synchronize()
     gather_ms = (time.perf_counter() - t_g) * 1e3
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, engines, allp)
+
     seq = None
-    if not args.no_sequence:
+    if args.full and not args.no_sequence:
         try:                          # a secondary measurement never costs the headline line
             seq = sequence_leg(device, args.seed, rank, world, per_gpu=args.seq_chains or seq_chains_for(world),
                                groups=args.seq_groups, overlap=args.seq_overlap)
@@ -832,7 +898,9 @@ def main():
         # the windowed `value` (chain-steps of overlapping windows)
         out["seq00_frames_per_s"] = seq.get("frames_per_s")
 
-    if world == 1 and args.cpu_frames > 2 and not args.no_single:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and world == 1 and args.cpu_frames > 2 and not args.no_single:
         sample = render_windows(rend, gt, [0], gap, args.cpu_frames - 2, device)[:, 0]
         pos_gpu, st, lat, lat_g, same = gpu_chain_positions(Kmat, opts, sample, device)
         out["single_chain"] = {"frames_per_s": round(1.0 / lat, 1), "ms_per_frame": round(lat * 1e3, 3),
@@ -864,7 +932,7 @@ def main():
             out["cpu_baseline"] = None
     else:
         out["cpu_baseline"] = None
-    if world == 1 and not args.no_match:
+    if args.full and world == 1 and not args.no_match:
         for key, leg in (("c3_sift_match", c3_leg), ("c5_sift_match", c5_sift_leg), ("c5_hd1080", c5_leg)):
             try:                      # secondary configurations never cost the headline line
                 out[key] = leg(device)

@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s)
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors of vo_dims / vo_opts / vo_state / vo_sift_buf have the C sizes."""
     src = r'''
     #include <stdio.h>
@@ -35,7 +35,7 @@ def test_struct_layouts_match_header():
         return 0;
     }'''
     inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    tmp = "/tmp/vo_abi_layout"
+    tmp = str(tmp_path / "vo_abi_layout")
     with open(tmp + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-I", inc, tmp + ".c", "-o", tmp], check=True)

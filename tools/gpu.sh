@@ -37,7 +37,7 @@ smoke)
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${tag}_smoke.log 2>&1
   rc=$?; tail -2 $O/${tag}_smoke.log; exit $rc ;;
 bench)
-  timeout -k 10 900 python -u bench.py "$@" > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }
+  timeout -k 10 900 python -u bench.py --full "$@" > $O/$tag.json 2> $O/$tag.err || { tail -20 $O/$tag.err; exit 1; }
   summ $O/$tag.json $tag ;;
 ab)
   reps=$1; A=$2; B=$3; shift 3
@@ -88,7 +88,7 @@ slicetl)   # kernel timeline + by-grid stats of one sequence rank slice: slicetl
   rm -f $O/stl_$tag/*kernel_trace.csv
   tail -2 $O/stl_$tag.log; head -25 $O/stl_${tag}_by_grid.csv ;;
 trace)
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o run -- python bench.py "$@" > $O/prof_$tag.json 2> $O/prof_$tag.err || exit $?
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o run -- python bench.py --full "$@" > $O/prof_$tag.json 2> $O/prof_$tag.err || exit $?
   python3 tools/trace_by_grid.py $O/prof_$tag $O/prof_${tag}_by_grid.csv
   rm -f $O/prof_$tag/*kernel_trace.csv
   head -30 $O/prof_${tag}_by_grid.csv ;;
