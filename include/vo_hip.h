@@ -208,7 +208,9 @@ int vo_status_word(const vo_state* s, int32_t* dst, vo_stream_t stream);
 /* ---- single-call primitives for the cv2 surface (B1) --------------------------- */
 
 /* cv2.calcOpticalFlowPyrLK (:281,287): points [B][n] with per-chain counts, using the
- * pyramids/derivatives already in state (prev = pyr[prev], next = pyr[1-prev]). */
+ * pyramids/derivatives already in state (prev = pyr[prev], next = pyr[1-prev]).  Windows
+ * (vo_opts.win_w, win_h) of 3 to 32 pixels per side and at most 1024 pixels; anything else
+ * returns VO_EARG with the outputs untouched (vo_track and vo_track_lk likewise). */
 int vo_lk_points(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
                  const float* pts, const int32_t* counts, int32_t cap, float* out_pts,
                  uint8_t* out_status, float* out_err, vo_stream_t stream);

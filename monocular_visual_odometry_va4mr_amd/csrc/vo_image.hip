@@ -292,7 +292,8 @@ __global__ void __launch_bounds__(256) k_pyr01(PyrLevelArgs A0, PyrLevelArgs A1,
 // at the level's first and last row).  Same bytes and derivatives as pyr_tile.
 #define PR_STEP 248
 // one wave's item of a level: strip sx, rows sy R .. sy R + R - 1, chain b
-template <bool L0>
+// RAGGED (level 0): the frame's byte count is no multiple of 4, see ld_dw
+template <bool L0, bool RAGGED = false>
 VO_DEV void pyr_rows_wave(const PyrLevelArgs& A, int R, int sx, int sy, int b)
 {
     const int lane = lane_id();
@@ -382,12 +383,28 @@ VO_DEV void pyr_rows_wave(const PyrLevelArgs& A, int R, int sx, int sy, int b)
         *(uint4*)dq = make_uint4(o[0], o[1], o[2], o[3]);
     };
     if constexpr (L0) {
+        // A dword load that crosses the end of the chain's buffer returns 0 as a whole, so when
+        // the frame's byte count is no multiple of 4 (131x67, 1242x375) its last 1-3 pixels are
+        // fetched as bytes (which read 0 past the end on their own).
+        // Frames of whole dwords keep the plain instantiation (vo_pyr_build picks it).
+        auto ld_dw = [&](int o) -> uint32_t {
+            uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0);
+            if constexpr (RAGGED) {
+                const int fbytes = (int)A.sstride;
+                if (o < fbytes && o + 4 > fbytes) {
+                    v = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) v |= (uint32_t)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, o + k, 0, 0) << (8 * k);
+                }
+            }
+            return v;
+        };
         // frame row y: bytes px - B .. px - B + 3 (byte align shift uniform over the wave)
         auto ld_row = [&](int y, uint32_t& d0, uint32_t& d1) {
             const int ro = y * wo + base - VO_BORDER;
             const int al = (ro & ~3) + 4 * lane;
-            d0 = __builtin_amdgcn_raw_buffer_load_b32(rs, al, 0, 0);
-            d1 = __builtin_amdgcn_raw_buffer_load_b32(rs, al + 4, 0, 0);
+            d0 = ld_dw(al);
+            d1 = ld_dw(al + 4);
         };
         auto val = [&](int y, uint32_t d0, uint32_t d1) {
             return fix(__builtin_amdgcn_alignbyte(d1, d0, (uint32_t)((y * wo + base - VO_BORDER) & 3)));
@@ -479,10 +496,10 @@ VO_DEV void pyr_rows_wave(const PyrLevelArgs& A, int R, int sx, int sy, int b)
     }
 }
 
-template <bool L0>
+template <bool L0, bool RAGGED = false>
 __global__ void __launch_bounds__(64) k_pyr_rows(PyrLevelArgs A, int R)
 {
-    pyr_rows_wave<L0>(A, R, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+    pyr_rows_wave<L0, RAGGED>(A, R, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // The small pyrDown levels of few chains in one launch (round 5): one 16-wave block per chain
@@ -671,7 +688,31 @@ VO_DEV uint32_t pack_w(int w00, int w01, int w10, int w11, int shift, int mask)
            ((uint32_t)((w10 >> shift) & mask) << 16) | ((uint32_t)((w11 >> shift) & mask) << 24);
 }
 
-template <int MAXJ>
+// Four bilinear taps (x, y) .. (x + 1, y + 1) of a window that may reach past the materialised
+// border (a side > VO_BORDER): byte offsets inside the level at reflect-101 coordinates, which
+// are the values a wider border would hold, and whether each tap lies in the interior (the
+// derivative image is zero everywhere else).  Every offset is that of an interior pixel.
+struct LKTaps {
+    int o00, o01, o10, o11;
+    bool in00, in01, in10, in11;
+};
+VO_DEV LKTaps lk_taps(int x, int y, int cols, int rows, int pitch)
+{
+    const int x0 = refl101(x, cols) + VO_BORDER, x1 = refl101(x + 1, cols) + VO_BORDER;
+    const int r0 = (refl101(y, rows) + VO_BORDER) * pitch, r1 = (refl101(y + 1, rows) + VO_BORDER) * pitch;
+    const bool ix0 = (unsigned)x < (unsigned)cols, ix1 = (unsigned)(x + 1) < (unsigned)cols;
+    const bool iy0 = (unsigned)y < (unsigned)rows, iy1 = (unsigned)(y + 1) < (unsigned)rows;
+    LKTaps t;
+    t.o00 = r0 + x0; t.o01 = r0 + x1; t.o10 = r1 + x0; t.o11 = r1 + x1;
+    t.in00 = ix0 && iy0; t.in01 = ix1 && iy0; t.in10 = ix0 && iy1; t.in11 = ix1 && iy1;
+    return t;
+}
+
+// BIG: a window side exceeds VO_BORDER, so a window accepted by the bounds test (ipx >= -win_w,
+// ipx < cols) can reach up to win - VO_BORDER pixels past the stored border.  Those instantiations
+// address every tap through lk_taps (window gather, J staging, level-0 error pass); the others
+// read the materialised border directly.
+template <int MAXJ, bool BIG>
 __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
 {
     extern __shared__ uint32_t lk_tile[];
@@ -696,7 +737,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
     const float sc = (float)(1. / (1 << level));
     // per-lane window slots: offsets in the level image and in the tile; slots past the
     // window read pixel (0,0) and are zeroed through their gradients / the error mask
-    int goff[MAXJ], toff[MAXJ];
+    int goff[MAXJ], toff[MAXJ], wxy[MAXJ];     // wxy (BIG): the slot's window position, wx | wy << 8
     bool live[MAXJ];
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
@@ -705,6 +746,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
         live[j] = k < npx;
         goff[j] = live[j] ? wy * pitch + wx : 0;
         toff[j] = live[j] ? wy * TW + wx : 0;
+        wxy[j] = live[j] ? (wx | (wy << 8)) : 0;
     }
     for (int p = pb * wpb + wave_id(); p < ntot; p += nb * wpb) {
         const float* src = (p < n0) ? (P.p0 + ((int64_t)b * P.cap0 + p) * 2) : (P.p1 + ((int64_t)b * P.cap1 + (p - n0)) * 2);
@@ -734,13 +776,25 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
             const int64_t ib = (int64_t)(ipy + VO_BORDER) * pitch + (ipx + VO_BORDER);
 #pragma unroll
             for (int j = 0; j < MAXJ; ++j) {
-                const int64_t o = ib + goff[j];
-                const uint8_t* s = I + o;
-                const int16_t* d = DI + 2 * o;              // (dx, dy) pairs
-                const int16_t* e = d + 1;
-                const int v = DESCALE(__mul24(s[0], iw00) + __mul24(s[1], iw01) + __mul24(s[pitch], iw10) + __mul24(s[pitch + 1], iw11), 9);
-                const int gx = DESCALE(__mul24(d[0], iw00) + __mul24(d[2], iw01) + __mul24(d[2 * pitch], iw10) + __mul24(d[2 * pitch + 2], iw11), 14);
-                const int gy = DESCALE(__mul24(e[0], iw00) + __mul24(e[2], iw01) + __mul24(e[2 * pitch], iw10) + __mul24(e[2 * pitch + 2], iw11), 14);
+                int v, gx, gy;
+                if constexpr (BIG) {
+                    const LKTaps t = lk_taps(ipx + (wxy[j] & 255), ipy + (wxy[j] >> 8), cols, rows, pitch);
+                    v = DESCALE(__mul24(I[t.o00], iw00) + __mul24(I[t.o01], iw01) + __mul24(I[t.o10], iw10) + __mul24(I[t.o11], iw11), 9);
+                    const int x00 = t.in00 ? DI[2 * t.o00] : 0, x01 = t.in01 ? DI[2 * t.o01] : 0;
+                    const int x10 = t.in10 ? DI[2 * t.o10] : 0, x11 = t.in11 ? DI[2 * t.o11] : 0;
+                    const int y00 = t.in00 ? DI[2 * t.o00 + 1] : 0, y01 = t.in01 ? DI[2 * t.o01 + 1] : 0;
+                    const int y10 = t.in10 ? DI[2 * t.o10 + 1] : 0, y11 = t.in11 ? DI[2 * t.o11 + 1] : 0;
+                    gx = DESCALE(__mul24(x00, iw00) + __mul24(x01, iw01) + __mul24(x10, iw10) + __mul24(x11, iw11), 14);
+                    gy = DESCALE(__mul24(y00, iw00) + __mul24(y01, iw01) + __mul24(y10, iw10) + __mul24(y11, iw11), 14);
+                } else {
+                    const int64_t o = ib + goff[j];
+                    const uint8_t* s = I + o;
+                    const int16_t* d = DI + 2 * o;              // (dx, dy) pairs
+                    const int16_t* e = d + 1;
+                    v = DESCALE(__mul24(s[0], iw00) + __mul24(s[1], iw01) + __mul24(s[pitch], iw10) + __mul24(s[pitch + 1], iw11), 9);
+                    gx = DESCALE(__mul24(d[0], iw00) + __mul24(d[2], iw01) + __mul24(d[2 * pitch], iw10) + __mul24(d[2 * pitch + 2], iw11), 14);
+                    gy = DESCALE(__mul24(e[0], iw00) + __mul24(e[2], iw01) + __mul24(e[2 * pitch], iw10) + __mul24(e[2 * pitch + 2], iw11), 14);
+                }
                 ival[j] = live[j] ? v : 0;
                 ixv[j] = live[j] ? gx : 0;
                 iyv[j] = live[j] ? gy : 0;
@@ -768,8 +822,8 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                     break;
                 }
                 if (inx < tx0 || inx > tx0 + 2 * LK_M || iny < ty0 || iny > ty0 + 2 * LK_M) {
-                    // (re)stage the quad tile around the window; bytes outside the padded
-                    // level are never read by an in-bounds window
+                    // (re)stage the quad tile around the window; with sides <= VO_BORDER bytes
+                    // outside the padded level are never read by an in-bounds window
                     tx0 = inx - LK_M;
                     ty0 = iny - LK_M;
                     __builtin_amdgcn_wave_barrier();
@@ -777,7 +831,11 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                         const int r = q / TW, c = q - r * TW;
                         const int gy = ty0 + r + VO_BORDER, gx = tx0 + c + VO_BORDER;
                         uint32_t v = 0;
-                        if (gy >= 0 && gy + 1 < prow && gx >= 0 && gx + 1 < pitch) {
+                        if constexpr (BIG) {
+                            const LKTaps t = lk_taps(tx0 + c, ty0 + r, cols, rows, pitch);
+                            v = (uint32_t)J[t.o00] | ((uint32_t)J[t.o01] << 8) | ((uint32_t)J[t.o10] << 16) |
+                                ((uint32_t)J[t.o11] << 24);
+                        } else if (gy >= 0 && gy + 1 < prow && gx >= 0 && gx + 1 < pitch) {
                             const uint8_t* g = J + (int64_t)gy * pitch + gx;
                             v = (uint32_t)g[0] | ((uint32_t)g[1] << 8) | ((uint32_t)g[pitch] << 16) |
                                 ((uint32_t)g[pitch + 1] << 24);
@@ -851,8 +909,14 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                 int es = 0;
 #pragma unroll
                 for (int j = 0; j < MAXJ; ++j) {
-                    const uint8_t* s = J + jb + goff[j];
-                    const int diff = DESCALE(__mul24(s[0], iw00) + __mul24(s[1], iw01) + __mul24(s[pitch], iw10) + __mul24(s[pitch + 1], iw11), 9) - ival[j];
+                    int diff;
+                    if constexpr (BIG) {
+                        const LKTaps t = lk_taps(inx + (wxy[j] & 255), iny + (wxy[j] >> 8), cols, rows, pitch);
+                        diff = DESCALE(__mul24(J[t.o00], iw00) + __mul24(J[t.o01], iw01) + __mul24(J[t.o10], iw10) + __mul24(J[t.o11], iw11), 9) - ival[j];
+                    } else {
+                        const uint8_t* s = J + jb + goff[j];
+                        diff = DESCALE(__mul24(s[0], iw00) + __mul24(s[1], iw01) + __mul24(s[pitch], iw10) + __mul24(s[pitch + 1], iw11), 9) - ival[j];
+                    }
                     es += live[j] ? (diff < 0 ? -diff : diff) : 0;
                 }
                 errv = (float)wave_sum_dpp(es) / (float)(32 * ww * wh);
@@ -2328,7 +2392,12 @@ struct SelSplitParams {
     const int32_t* chain_status;
 };
 
-VO_DEV uint32_t* gs_hist(const SelSplitParams& P, int b) { return (uint32_t*)(P.sorted + (int64_t)b * P.sstride + P.ccap); }
+// the histogram takes uint4 accesses: its start is rounded up to 16 bytes (an odd ccap, or an odd
+// chain stride, leaves the key area's end only 8-byte aligned; the 4096-u64 extra has the room)
+VO_DEV uint32_t* gs_hist(const SelSplitParams& P, int b)
+{
+    return (uint32_t*)(((uintptr_t)(P.sorted + (int64_t)b * P.sstride + P.ccap) + 15) & ~(uintptr_t)15);
+}
 VO_DEV int32_t* gs_npass(const SelSplitParams& P, int b) { return (int32_t*)(gs_hist(P, b) + GS_NB); }
 
 // the chain's gate and bucket map: keys >= lo pass; bucket(k) = (kmax - (k >> 32)) >> shift
@@ -2713,7 +2782,8 @@ extern "C" int vo_pyr_build(const vo_dims* d, const vo_state* s, int cur, const 
             int R = 16;
             while (R > 4 && (int64_t)ns * ((A.h + R - 1) / R) * d->B < 8192) R >>= 1;
             dim3 g(ns, (A.h + R - 1) / R, d->B);
-            if (l == 0) hipLaunchKernelGGL(k_pyr_rows<true>, g, dim3(64), 0, VO_STREAM(stream), A, R);
+            if (l == 0 && (frame_stride & 3)) hipLaunchKernelGGL((k_pyr_rows<true, true>), g, dim3(64), 0, VO_STREAM(stream), A, R);
+            else if (l == 0) hipLaunchKernelGGL(k_pyr_rows<true>, g, dim3(64), 0, VO_STREAM(stream), A, R);
             else hipLaunchKernelGGL(k_pyr_rows<false>, g, dim3(64), 0, VO_STREAM(stream), A, R);
             continue;
         }
@@ -2787,7 +2857,7 @@ static void fill_lk(LKParams& P, const vo_dims* d, const vo_opts* o, const vo_st
 static int launch_lk(const LKParams& P, int B, hipStream_t st)
 {
     const int npx = P.win_w * P.win_h;
-    if (P.win_w <= 2 || P.win_h <= 2 || npx > 64 * 16 || B < 1) return VO_EARG;
+    if (P.win_w <= 2 || P.win_h <= 2 || P.win_w > 32 || P.win_h > 32 || npx > 64 * 16 || B < 1) return VO_EARG;
     // One wave per block (iteration counts differ wildly between points, so a wave's slot
     // must free as soon as its own points are done), 2048 blocks per chain.
     static const int nb_env = [] { const char* e = getenv("VO_LK_NB"); return e ? atoi(e) : 0; }();
@@ -2811,9 +2881,13 @@ static int launch_lk(const LKParams& P, int B, hipStream_t st)
         hipLaunchKernelGGL((k_lk_w<15, 15>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
         return hip_ok() ? VO_OK : VO_EHIP;
     }
+    // a side beyond the materialised border: the instantiations that reflect every tap
+    // (more than 256 pixels always has such a side)
+    const bool big = P.win_w > VO_BORDER || P.win_h > VO_BORDER;
     for (int level = P.L; level >= 0; --level) {
-        if (npx <= 256) hipLaunchKernelGGL(k_lk<4>, dim3(nblk), dim3(64), lds, st, P, level, B, nb);
-        else hipLaunchKernelGGL(k_lk<16>, dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        if (npx > 256) hipLaunchKernelGGL((k_lk<16, true>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else if (big) hipLaunchKernelGGL((k_lk<4, true>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else hipLaunchKernelGGL((k_lk<4, false>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
     }
     return hip_ok() ? VO_OK : VO_EHIP;
 }

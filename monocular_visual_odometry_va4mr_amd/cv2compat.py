@@ -110,6 +110,12 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, mask=None,
 def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), maxLevel=3,
                          criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0,
                          minEigThreshold=1e-4):
+    """cv2.calcOpticalFlowPyrLK without an initial flow.  Supported ``winSize``: 3 to 32 pixels per
+    side and at most 1024 pixels in all (the default 21x21 included); any other window raises
+    (vo_lk_points returns VO_EARG).  15x15 runs the one-launch kernel k_lk_w, every other size
+    the per-level k_lk; sides above the pyramid's 16-pixel border take the window's taps at
+    reflect-101 coordinates with zero derivatives outside the image, as OpenCV's winSize-wide
+    pyramid border does."""
     if flags != 0 or nextPts is not None:
         raise NotImplementedError("OPTFLOW_USE_INITIAL_FLOW / flags are not used by the reference")
     p = np.asarray(prevPts)

@@ -130,3 +130,29 @@ def test_select_flat_and_sparse_frames(kitti_frames, sel_mode):
             got, n = _corners(eng, b)
             ref = O.gftt(frames[b], 1400, 0.1, 10, 3)
             assert np.array_equal(got, ref), f"mode {mode} frame {b}: {n} vs {len(ref)}"
+
+
+def test_select_odd_ccap_three_chains(kitti_frames, sel_mode):
+    """1242x375 (a real KITTI size): the engine's key capacity ccap = W * H // 2 + 1024 is odd, so
+    the key area of gf_sort ends on an odd u64 offset for chains 0 and 2 (the chain stride
+    ccap + 4096 is odd too) and the histogram behind it, which takes uint4 accesses, must be
+    placed on its own 16-byte boundary.  Three chains on different frames, both forms, two calls
+    (the split form's zeroed scratch must be found again at the same aligned place)."""
+    from oracle import _olib as O
+    fr, K = kitti_frames
+    W, H, B = 1242, 375, 3
+    frames = np.stack([np.pad(fr[b][:H], ((0, 0), (0, W - fr[b].shape[1])), mode="edge") for b in range(B)])
+    assert frames.shape == (B, H, W)
+    refs = [O.gftt(frames[b], 1400, 0.1, 10, 3) for b in range(B)]
+    assert all(len(r) > 100 for r in refs)
+    for mode in (2, 1):
+        sel_mode(mode)
+        eng = _engine(K, B=B, W=W, H=H)
+        assert eng.dims.ccap % 2 == 1
+        eng.build_pyramid(frames, 0)
+        for call in range(2):
+            assert eng.lib.vo_gftt(eng._pd, eng._po, eng._ps, 0, eng.stream) == 0
+            torch.cuda.synchronize()
+            for b in range(B):
+                got, n = _corners(eng, b)
+                assert np.array_equal(got, refs[b]), f"mode {mode} call {call} chain {b}: {n} vs {len(refs[b])}"

@@ -126,6 +126,37 @@ def test_pyramid_tail_many_chains(engine_factory, W, H):
             ref = O.pyrdown(ref)
 
 
+@pytest.mark.parametrize("W,H,B,max_level", [(131, 67, 1, 0), (131, 67, 10, 3), (1242, 375, 9, 3), (130, 67, 1, 0), (129, 67, 3, 0)])
+def test_pyramid_rows_ragged_frame_bytes(engine_factory, W, H, B, max_level):
+    """Level 0 by the row-streaming kernel (k_pyr_rows<true>: a single-level pyramid, or more than
+    8 chains) on frames whose byte count W * H is no multiple of 4 (1, 2 and 3 bytes over): the
+    frame's last pixels sit in a dword that crosses the end of the chain's buffer.  Every chain's
+    levels, derivatives and reflect-101 border against the oracle."""
+    from oracle import _olib as O
+    from monocular_visual_odometry_va4mr_amd import _lib as L
+    assert (W * H) % 4 != 0
+    rng = np.random.default_rng(W * H + B)
+    imgs = rng.integers(0, 256, (B, H, W), dtype=np.uint8)
+    imgs[:, -1, -4:] |= 0x81                      # no zero among the last pixels (a dropped dword reads 0)
+    K = np.array([[300.0, 0, W / 2], [0, 300.0, H / 2], [0, 0, 1]])
+    eng, _ = engine_factory(K=K, B=B, W=W, H=H, maxLevel=max_level)
+    assert eng.dims.nlev == 1 or B > 8
+    eng.build_pyramid(torch.from_numpy(imgs), 0)
+    torch.cuda.synchronize()
+    d = eng.dims
+    Bd = L.VO_BORDER
+    for b in range(B):
+        ref = imgs[b]
+        for lv in range(d.nlev):
+            w, h, p, o = d.lvl_w[lv], d.lvl_h[lv], d.lvl_pitch[lv], d.lvl_off[lv]
+            pp = eng.t["pyr0"][b, o:o + (h + 2 * Bd) * p].view(h + 2 * Bd, p).cpu().numpy()[:, :w + 2 * Bd]
+            ry = [O_refl(i - Bd, h) for i in range(h + 2 * Bd)]
+            rx = [O_refl(i - Bd, w) for i in range(w + 2 * Bd)]
+            assert np.array_equal(pp, ref[np.ix_(ry, rx)]), f"b={b} pyramid level {lv}"
+            assert np.array_equal(eng.deriv_level(lv, b, which=0), O.scharr(ref)), f"b={b} scharr level {lv}"
+            ref = O.pyrdown(ref)
+
+
 def O_refl(p, n):
     """cv::borderInterpolate(BORDER_REFLECT_101)"""
     if n == 1:
