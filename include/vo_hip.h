@@ -215,6 +215,38 @@ int vo_lk_points(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev
                  const float* pts, const int32_t* counts, int32_t cap, float* out_pts,
                  uint8_t* out_status, float* out_err, vo_stream_t stream);
 
+/* cv2.calcOpticalFlowPyrLK's flags (OpenCV's values) */
+#define VO_LK_USE_INITIAL_FLOW   4
+#define VO_LK_GET_MIN_EIGENVALS  8
+
+/* vo_lk_points with cv2's flags.  VO_LK_USE_INITIAL_FLOW: point i's estimate starts at
+ * init[i] * 2^-L at the top level L instead of at pts[i] * 2^-L; init is [B][cap][2], read only with
+ * that bit (else it may be NULL), and a distinct buffer from out_pts.  VO_LK_GET_MIN_EIGENVALS:
+ * out_err receives the minimum eigenvalue of level 0's tensor (the value compared with
+ * vo_opts.min_eig) wherever the level-0 window of pts[i] is in bounds, whatever the status, and
+ * the L1 error pass does not run.  Any other flag bit, or bit 4 with init NULL: VO_EARG with the
+ * outputs untouched.  flags = 0 is vo_lk_points. */
+int vo_lk_points_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
+                    const float* pts, const float* init, const int32_t* counts, int32_t cap,
+                    int32_t flags, float* out_pts, uint8_t* out_status, float* out_err,
+                    vo_stream_t stream);
+
+/* vo_lk_points_ex followed by the forward-backward gate: every point tracked forward (status 1) is
+ * tracked back from its result, next to prev, with flags 0 and the same window, levels, criteria
+ * and min_eig, into back_pts [B][cap][2] (unspecified where the forward status is 0).  out_status
+ * is 1 iff both passes succeeded and the point came back within fb_threshold pixels of pts[i]
+ * ((double)dx * dx + (double)dy * dy <= fb_threshold^2 with float dx, dy); out_pts and out_err are
+ * the forward pass's.  fb_threshold > 0 and finite, else VO_EARG with the outputs untouched. */
+int vo_lk_points_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
+                    const float* pts, const float* init, const int32_t* counts, int32_t cap,
+                    int32_t flags, double fb_threshold, float* back_pts, float* out_pts,
+                    uint8_t* out_status, float* out_err, vo_stream_t stream);
+
+/* vo_track (compact = 1) or vo_track_lk (compact = 0) with the forward-backward gate applied to
+ * trk_st before any filtering; scratch: [B][ncap + pcap][2] floats (the points tracked back). */
+int vo_track_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, double fb_threshold,
+                float* scratch, int compact, vo_stream_t stream);
+
 /* cv2.solvePnPRansac(..., SOLVEPNP_P3P) (:343) on [B][cap] points with counts.
  * out: rvec[B][3], tvec[B][3], success[B], inlier mask [B][cap] (u8), n_inl[B]. */
 int vo_pnp_ransac(const vo_opts* o, int B, const float* obj, const float* img,

@@ -20,6 +20,11 @@ per frame), so eager is the default.  The reference's failur
 conditions raise the same exceptions: ValueError("Not enough keypoints for PnP") (:358),
 ValueError("PnP failed") (:352), and the crashes the reference would hit when
 goodFeaturesToTrack yields 0 / 1 corners (:256-258).
+
+The options dict goes to the engine unchanged, so this build's own keys ride along with the
+reference's: ``sift_nfeatures``, and ``lk_fb_threshold`` (pixels; absent or None = off), which
+drops every tracked point that LK from the new frame back to the old one does not return to
+within that distance of where it started (vo_track_fb).
 """
 from __future__ import annotations
 

@@ -16,6 +16,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 VO_MAX_LEVELS = 8
 VO_BORDER = 16
+VO_LK_USE_INITIAL_FLOW = 4
+VO_LK_GET_MIN_EIGENVALS = 8
 
 ST_OK = 0
 ST_NOT_ENOUGH_KP = 1
@@ -147,6 +149,9 @@ def _declare(L):
         "vo_add_corners_finish": ([D, O, S, P], C.c_int),
         "vo_status_word": ([S, P, P], C.c_int),
         "vo_lk_points": ([D, O, S, C.c_int, P, P, i32, P, P, P, P], C.c_int),
+        "vo_lk_points_ex": ([D, O, S, C.c_int, P, P, P, i32, i32, P, P, P, P], C.c_int),
+        "vo_lk_points_fb": ([D, O, S, C.c_int, P, P, P, i32, i32, f64, P, P, P, P, P], C.c_int),
+        "vo_track_fb": ([D, O, S, C.c_int, f64, P, C.c_int, P], C.c_int),
         "vo_pnp_ransac": ([O, C.c_int, P, P, P, i32, P, P, P, P, P, P, i64, P], C.c_int),
         "vo_triangulate_points": ([C.c_int, P, P, P, P, P, P], C.c_int),
         "vo_rodrigues": ([C.c_int, C.c_int, P, P, P], C.c_int),

@@ -587,6 +587,14 @@ struct LKParams {
     uint8_t* st;
     float* err;
     int ocap;
+    // read by the EX instantiations alone (vo_lk_points_ex, vo_lk_points_fb, vo_track_fb)
+    const float* init;              // OPTFLOW_USE_INITIAL_FLOW: [B][ocap][2], the estimate's start at level L (or null)
+    int eig_err;                    // OPTFLOW_LK_GET_MIN_EIGENVALS: err = level 0's minEig, no L1 error pass
+    // backward pass of the forward-backward gate (or null): the point tracked is fwd[oidx] (the
+    // forward result), only where st[oidx] (the forward status) is 1; the segment point is where
+    // it has to return to, and st[oidx] becomes the gate status && |out - point|^2 <= thr2
+    const float* fwd;
+    double thr2;
 };
 
 // Block -> (chain, point block).  With B >= 8 all blocks of one chain land on one XCD
@@ -712,7 +720,9 @@ VO_DEV LKTaps lk_taps(int x, int y, int cols, int rows, int pitch)
 // ipx < cols) can reach up to win - VO_BORDER pixels past the stored border.  Those instantiations
 // address every tap through lk_taps (window gather, J staging, level-0 error pass); the others
 // read the materialised border directly.
-template <int MAXJ, bool BIG>
+// EX: the variants behind cv2's flags and the forward-backward gate (LKParams::init, eig_err, fwd);
+// the default instantiations hold none of that code.
+template <int MAXJ, bool BIG, bool EX = false>
 __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
 {
     extern __shared__ uint32_t lk_tile[];
@@ -751,12 +761,25 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
     for (int p = pb * wpb + wave_id(); p < ntot; p += nb * wpb) {
         const float* src = (p < n0) ? (P.p0 + ((int64_t)b * P.cap0 + p) * 2) : (P.p1 + ((int64_t)b * P.cap1 + (p - n0)) * 2);
         const int64_t oidx = (int64_t)b * P.ocap + p;
-        const float ptx = src[0], pty = src[1];
+        float ptx = src[0], pty = src[1];
+        const float gtx = ptx, gty = pty;       // EX: the gate's origin
+        if constexpr (EX) {
+            if (P.fwd) {
+                if (!P.st[oidx]) continue;      // lost by the forward pass: nothing to track back
+                ptx = P.fwd[2 * oidx];
+                pty = P.fwd[2 * oidx + 1];
+            }
+        }
         int status = 1;
         float errv = 0.f;
         float px = ptx * sc, py = pty * sc;
         float ox, oy;   // nextPts[ptidx]
-        if (level == P.L) { ox = px; oy = py; }
+        if (level == P.L) {
+            ox = px; oy = py;
+            if constexpr (EX) {
+                if (P.init) { ox = P.init[2 * oidx] * sc; oy = P.init[2 * oidx + 1] * sc; }
+            }
+        }
         else { ox = P.out[2 * oidx] * 2.f; oy = P.out[2 * oidx + 1] * 2.f; }
         px -= hx;
         py -= hy;
@@ -807,6 +830,9 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
             const float A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
             float D = A11 * A22 - A12 * A12;
             const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * ww * wh);
+            if constexpr (EX) {
+                if (P.eig_err && level == 0) errv = minEig;
+            }
             if (minEig < P.min_eig || D < FLT_EPSILON) {
                 if (level == 0) status = 0;
                 break;
@@ -893,7 +919,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                 pdx = ddx;
                 pdy = ddy;
             }
-            if (status && level == 0) {
+            if (status && level == 0 && !(EX && P.eig_err)) {
                 const float fx = ox - hx, fy = oy - hy;
                 const int inx = (int)floorf(fx), iny = (int)floorf(fy);
                 if (inx < -ww || inx >= cols || iny < -wh || iny >= rows) {
@@ -926,6 +952,12 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
             P.out[2 * oidx] = ox;
             P.out[2 * oidx + 1] = oy;
             if (level == 0) {
+                if constexpr (EX) {
+                    if (P.fwd) {
+                        const float gdx = ox - gtx, gdy = oy - gty;
+                        if (!((double)gdx * gdx + (double)gdy * gdy <= P.thr2)) status = 0;
+                    }
+                }
                 P.st[oidx] = (uint8_t)status;
                 if (P.err) P.err[oidx] = errv;
             }
@@ -980,7 +1012,7 @@ __device__ long long g_lkprof[VO_MAX_LEVELS][1024][8];
 // may run up to 3 bytes past a row end (next row, or the >= 64-byte tail slack that the
 // caller must leave after each pyramid -- launch_lk checks it).  Arithmetic is identical to
 // k_lk (bit-exact with the CPU restatement).
-template <int WW, int WH>
+template <int WW, int WH, bool EX = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_lk_w(LKParams P, int level_hi, int level_lo, int B, int nb, int xcd)
 {
     constexpr int WPB = 1;
@@ -1133,8 +1165,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #endif
         // per-point values are wave-uniform: keep them (and the addresses built from them)
         // in scalar registers
-        const float ptx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(src[0])));
-        const float pty = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(src[1])));
+        float ptx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(src[0])));
+        float pty = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(src[1])));
+        const float gtx = ptx, gty = pty;       // EX: the gate's origin
+        if constexpr (EX) {
+            if (P.fwd) {
+                if (!__builtin_amdgcn_readfirstlane((int)P.st[oidx])) continue;   // lost by the forward pass
+                ptx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.fwd[2 * oidx])));
+                pty = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.fwd[2 * oidx + 1])));
+            }
+        }
         int status = 1;
         float errv = 0.f;
         float ox = 0.f, oy = 0.f;   // nextPts[ptidx]
@@ -1143,7 +1183,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
         const unsigned colsW = (unsigned)(cols + WW), rowsW = (unsigned)(rows + WH);
         const float sc = __builtin_ldexpf(1.f, -level);     // 1 / 2^level, exact (no f64 division)
         float px = ptx * sc, py = pty * sc;
-        if (level == P.L) { ox = px; oy = py; }
+        if (level == P.L) {
+            ox = px; oy = py;
+            if constexpr (EX) {
+                if (P.init) {
+                    ox = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.init[2 * oidx]))) * sc;
+                    oy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.init[2 * oidx + 1]))) * sc;
+                }
+            }
+        }
         else if (level == level_hi) {
             ox = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.out[2 * oidx]))) * 2.f;
             oy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.out[2 * oidx + 1]))) * 2.f;
@@ -1292,6 +1340,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
                 const float inv_n = 1.f / (float)(2 * WW * WH);
                 const float ma = (sum2 - sa) * inv_n;
                 const float mg = __builtin_fmaf(0x1p-20f, (sa + sum2) * inv_n + fabsf(ma), 0x1p-100f);
+                if constexpr (EX) {
+                    if (P.eig_err && level == 0) errv = (sum2 - sqrtf(tq)) / (float)(2 * WW * WH);
+                }
                 bool reject;
                 if (ma + mg < P.min_eig) reject = true;
                 else if (ma - mg >= P.min_eig) reject = false;
@@ -1403,7 +1454,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #ifdef VO_LKX_NOERR
                 if (false) {
 #else
-                if (status && level == 0) {
+                if (status && level == 0 && !(EX && P.eig_err)) {
 #endif
                     const float fx = ox - hx, fy = oy - hy;
                     const int inx = (int)floorf(fx), iny = (int)floorf(fy);
@@ -1440,6 +1491,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
             P.out[2 * oidx] = ox;
             P.out[2 * oidx + 1] = oy;
             if (level_lo == 0) {
+                if constexpr (EX) {
+                    if (P.fwd) {
+                        const float gdx = ox - gtx, gdy = oy - gty;
+                        if (!((double)gdx * gdx + (double)gdy * gdy <= P.thr2)) status = 0;
+                    }
+                }
                 P.st[oidx] = (uint8_t)status;
                 if (P.err) P.err[oidx] = errv;
             }
@@ -2852,9 +2909,14 @@ static void fill_lk(LKParams& P, const vo_dims* d, const vo_opts* o, const vo_st
         P.eps2_lo = -INFINITY;
         P.eps2_hi = INFINITY;
     }
+    P.init = nullptr;
+    P.eig_err = 0;
+    P.fwd = nullptr;
+    P.thr2 = 0.;
 }
 
-static int launch_lk(const LKParams& P, int B, hipStream_t st)
+template <bool EX>
+static int launch_lk_t(const LKParams& P, int B, hipStream_t st)
 {
     const int npx = P.win_w * P.win_h;
     if (P.win_w <= 2 || P.win_h <= 2 || P.win_w > 32 || P.win_h > 32 || npx > 64 * 16 || B < 1) return VO_EARG;
@@ -2878,17 +2940,92 @@ static int launch_lk(const LKParams& P, int B, hipStream_t st)
     // sizes (cv2.calcOpticalFlowPyrLK's default 21x21 on the cv2compat surface): k_lk, one
     // launch per level.
     if (staged15) {
-        hipLaunchKernelGGL((k_lk_w<15, 15>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
+        hipLaunchKernelGGL((k_lk_w<15, 15, EX>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
         return hip_ok() ? VO_OK : VO_EHIP;
     }
     // a side beyond the materialised border: the instantiations that reflect every tap
     // (more than 256 pixels always has such a side)
     const bool big = P.win_w > VO_BORDER || P.win_h > VO_BORDER;
     for (int level = P.L; level >= 0; --level) {
-        if (npx > 256) hipLaunchKernelGGL((k_lk<16, true>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
-        else if (big) hipLaunchKernelGGL((k_lk<4, true>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
-        else hipLaunchKernelGGL((k_lk<4, false>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        if (npx > 256) hipLaunchKernelGGL((k_lk<16, true, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else if (big) hipLaunchKernelGGL((k_lk<4, true, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else hipLaunchKernelGGL((k_lk<4, false, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
     }
+    return hip_ok() ? VO_OK : VO_EHIP;
+}
+
+static int launch_lk(const LKParams& P, int B, hipStream_t st) { return launch_lk_t<false>(P, B, st); }
+
+// The backward pass of the forward-backward gate for the forward call F (already launched on st):
+// LK with flags 0 from next to prev (fill_lk with the roles swapped gives the other pyramid's
+// derivatives) of F's results where F's status is 1, into `back`; each wave then writes its point's
+// gate over F's status.  F's point segments stay: they give the count and the gate's origin.
+static int launch_lk_back(const LKParams& F, const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
+                          double thr, float* back, hipStream_t st)
+{
+    LKParams P;
+    fill_lk(P, d, o, s, 1 - prev);
+    P.p0 = F.p0; P.n0 = F.n0; P.cap0 = F.cap0;
+    P.p1 = F.p1; P.n1 = F.n1; P.cap1 = F.cap1; P.seg1_min = F.seg1_min;
+    P.chain_status = F.chain_status;
+    P.out = back; P.st = F.st; P.err = nullptr; P.ocap = F.ocap;
+    P.fwd = F.out;
+    P.thr2 = thr * thr;
+    return launch_lk_t<true>(P, d->B, st);
+}
+
+static bool lk_thr_ok(double thr) { return thr > 0. && thr <= DBL_MAX; }   // false for NaN too
+
+extern "C" int vo_lk_points_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* pts,
+                               const float* init, const int32_t* counts, int32_t cap, int32_t flags, float* out_pts,
+                               uint8_t* out_status, float* out_err, vo_stream_t stream)
+{
+    if (!d || !o || !s || !pts || !counts || !out_pts || !out_status || prev < 0 || prev > 1) return VO_EARG;
+    if ((flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)) || ((flags & VO_LK_USE_INITIAL_FLOW) && !init))
+        return VO_EARG;
+    LKParams P;
+    fill_lk(P, d, o, s, prev);
+    P.p0 = pts; P.n0 = counts; P.cap0 = cap;
+    P.p1 = nullptr; P.n1 = nullptr; P.cap1 = 0; P.seg1_min = 0;
+    P.chain_status = nullptr;
+    P.out = out_pts; P.st = out_status; P.err = out_err; P.ocap = cap;
+    if (!flags) return launch_lk(P, d->B, VO_STREAM(stream));
+    P.init = (flags & VO_LK_USE_INITIAL_FLOW) ? init : nullptr;
+    P.eig_err = (flags & VO_LK_GET_MIN_EIGENVALS) != 0;
+    return launch_lk_t<true>(P, d->B, VO_STREAM(stream));
+}
+
+extern "C" int vo_lk_points_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* pts,
+                               const float* init, const int32_t* counts, int32_t cap, int32_t flags,
+                               double fb_threshold, float* back_pts, float* out_pts, uint8_t* out_status,
+                               float* out_err, vo_stream_t stream)
+{
+    if (!back_pts || !lk_thr_ok(fb_threshold)) return VO_EARG;
+    int rc = vo_lk_points_ex(d, o, s, prev, pts, init, counts, cap, flags, out_pts, out_status, out_err, stream);
+    if (rc) return rc;
+    LKParams F = {};
+    F.p0 = pts; F.n0 = counts; F.cap0 = cap;
+    F.p1 = nullptr; F.n1 = nullptr; F.cap1 = 0; F.seg1_min = 0;
+    F.chain_status = nullptr;
+    F.out = out_pts; F.st = out_status; F.ocap = cap;
+    return launch_lk_back(F, d, o, s, prev, fb_threshold, back_pts, VO_STREAM(stream));
+}
+
+extern "C" int vo_track_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, double fb_threshold,
+                           float* scratch, int compact, vo_stream_t stream)
+{
+    if (!d || !o || !s || prev < 0 || prev > 1 || !scratch || !lk_thr_ok(fb_threshold)) return VO_EARG;
+    LKParams P;
+    fill_lk(P, d, o, s, prev);
+    P.p0 = s->lm_kp; P.n0 = s->nL; P.cap0 = d->ncap;
+    P.p1 = s->c_kp; P.n1 = s->nC; P.cap1 = d->pcap; P.seg1_min = 1;   // :286 "if P > 1"
+    P.chain_status = s->status;
+    P.out = s->trk_pts; P.st = s->trk_st; P.err = s->trk_err; P.ocap = d->ncap + d->pcap;
+    int rc = launch_lk(P, d->B, VO_STREAM(stream));
+    if (rc) return rc;
+    rc = launch_lk_back(P, d, o, s, prev, fb_threshold, scratch, VO_STREAM(stream));
+    if (rc || !compact) return rc;
+    hipLaunchKernelGGL(k_track_compact, dim3(d->B), dim3(256), 0, VO_STREAM(stream), *d, *s);
     return hip_ok() ? VO_OK : VO_EHIP;
 }
 

@@ -34,6 +34,8 @@ TERM_CRITERIA_COUNT = 1
 TERM_CRITERIA_MAX_ITER = 1
 TERM_CRITERIA_EPS = 2
 IMREAD_GRAYSCALE = 0
+OPTFLOW_USE_INITIAL_FLOW = 4
+OPTFLOW_LK_GET_MIN_EIGENVALS = 8
 NORM_L2 = 4
 
 
@@ -110,20 +112,33 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, mask=None,
 def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), maxLevel=3,
                          criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0,
                          minEigThreshold=1e-4):
-    """cv2.calcOpticalFlowPyrLK without an initial flow.  Supported ``winSize``: 3 to 32 pixels per
-    side and at most 1024 pixels in all (the default 21x21 included); any other window raises
-    (vo_lk_points returns VO_EARG).  15x15 runs the one-launch kernel k_lk_w, every other size
+    """cv2.calcOpticalFlowPyrLK.  ``flags``: OPTFLOW_USE_INITIAL_FLOW (each point's estimate starts
+    at ``nextPts``, float32 with as many points as ``prevPts``) and OPTFLOW_LK_GET_MIN_EIGENVALS
+    (``err`` is the minimum eigenvalue of the level-0 tensor, for every point whose window is in
+    bounds); any other bit raises NotImplementedError.  Without OPTFLOW_USE_INITIAL_FLOW a given
+    ``nextPts`` is ignored (OpenCV only uses it as the output buffer); no input array is written.
+    Supported ``winSize``: 3 to 32 pixels per side and at most 1024 pixels in all (the default
+    21x21 included); any other window raises (vo_lk_points_ex returns VO_EARG).  15x15 runs the one-launch kernel k_lk_w, every other size
     the per-level k_lk; sides above the pyramid's 16-pixel border take the window's taps at
     reflect-101 coordinates with zero derivatives outside the image, as OpenCV's winSize-wide
     pyramid border does."""
-    if flags != 0 or nextPts is not None:
-        raise NotImplementedError("OPTFLOW_USE_INITIAL_FLOW / flags are not used by the reference")
+    flags = int(flags)
+    if flags & ~(OPTFLOW_USE_INITIAL_FLOW | OPTFLOW_LK_GET_MIN_EIGENVALS):
+        raise NotImplementedError("only OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_LK_GET_MIN_EIGENVALS are supported")
     p = np.asarray(prevPts)
     if p.dtype != np.float32:
         raise error("prevPts must be float32 (checkVector(2, CV_32F))")
     shape = p.shape
     pts = np.ascontiguousarray(p.reshape(-1, 2))
     n = pts.shape[0]
+    ini = None
+    if flags & OPTFLOW_USE_INITIAL_FLOW:
+        if nextPts is None:
+            raise error("OPTFLOW_USE_INITIAL_FLOW needs nextPts")
+        q = np.asarray(nextPts)
+        if q.dtype != np.float32 or q.size != 2 * n:
+            raise error("nextPts must be float32 with as many points as prevPts (checkVector(2, CV_32F) == npoints)")
+        ini = np.ascontiguousarray(q.reshape(-1, 2))
     a, b = _gray(prevImg), _gray(nextImg)
     if a.shape != b.shape:
         raise error("prevImg and nextImg must have the same size")
@@ -141,8 +156,9 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), m
     out = torch.empty((1, n, 2), dtype=torch.float32, device=dev)
     st = torch.empty((1, n), dtype=torch.uint8, device=dev)
     err = torch.empty((1, n), dtype=torch.float32, device=dev)
-    L.check(eng.lib.vo_lk_points(eng._pd, eng._po, eng._ps, 0, _p(dp), _p(cnt), n, _p(out), _p(st), _p(err),
-                                 _stream()), "vo_lk_points")
+    di = None if ini is None else torch.from_numpy(ini).to(dev).reshape(1, n, 2)
+    L.check(eng.lib.vo_lk_points_ex(eng._pd, eng._po, eng._ps, 0, _p(dp), None if di is None else _p(di), _p(cnt), n,
+                                    flags, _p(out), _p(st), _p(err), _stream()), "vo_lk_points_ex")
     return (out.cpu().numpy().reshape(shape), st.cpu().numpy().reshape(-1, 1),
             err.cpu().numpy().reshape(-1, 1))
 

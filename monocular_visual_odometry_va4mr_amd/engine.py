@@ -22,7 +22,7 @@ and runtime ValueErrors of the reference become per-chain status codes (``status
 from __future__ import annotations
 
 import ctypes as C
-
+import math
 import os
 
 import numpy as np
@@ -185,6 +185,16 @@ class Engine:
         T["pnp_mask"] = z(B, ncap, dt=torch.uint8)
         T["work"] = z(B, d.work_stride, dt=torch.float64)
         T["iwork"] = z(B, d.iwork_stride, dt=torch.int32)
+        # lk_fb_threshold (pixels; this build's own key, absent / None = off as in the reference):
+        # tracking goes through vo_track_fb, which keeps a point only if LK from the new frame back
+        # to the old one returns within that distance of where it started
+        thr = options.get("lk_fb_threshold")
+        self.lk_fb_threshold = None if thr is None else float(thr)
+        self._fb_scratch = None
+        if self.lk_fb_threshold is not None:
+            if not (self.lk_fb_threshold > 0 and math.isfinite(self.lk_fb_threshold)):
+                raise ValueError("lk_fb_threshold must be a positive finite number of pixels (or None)")
+            self._fb_scratch = z(B, ncap + pcap, 2, dt=torch.float32)      # the points tracked back
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -352,6 +362,12 @@ class Engine:
         # first in each chain's block (one kernel boundary fewer on the step's critical path)
         defer = fused and os.environ.get("VO_COMPACT_IN_TRACK") != "1"      # =1: A/B option
         track = lib.vo_track_lk if defer else lib.vo_track
+        if self.lk_fb_threshold is not None:
+            fb_thr, fb_scr = C.c_double(self.lk_fb_threshold), C.c_void_p(self._fb_scratch.data_ptr())
+            compact = 0 if defer else 1
+
+            def track(pd, po, ps, prev, strm):
+                return lib.vo_track_fb(pd, po, ps, prev, fb_thr, fb_scr, compact, strm)
         ts = getattr(self, "track_stream", None)
         if ts is not None and forked and not gftt_late:
             # tracking on a stream shared by the engines of a batch (track_stream): their LK

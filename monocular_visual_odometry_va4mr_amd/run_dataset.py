@@ -55,14 +55,19 @@ def dataset_frames(dataset: str, path: str):
 
 
 def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str | None = "out/interface_plot.png",
-        plot_every: int = 0, poses_out: str | None = None, device=None, verbose: bool = False, K=None) -> dict:
+        plot_every: int = 0, poses_out: str | None = None, device=None, verbose: bool = False, K=None,
+        lk_fb_threshold: float | None = None) -> dict:
     """Run main.py's loop; returns a summary dict and (in "_vo") the pipeline object.
-    K overrides the dataset's intrinsics (e.g. for a synthetic sequence written to disk)."""
+    K overrides the dataset's intrinsics (e.g. for a synthetic sequence written to disk).
+    ``lk_fb_threshold`` (pixels): the engine's forward-backward gate on tracked points; None
+    (the reference's behaviour) leaves it off."""
     import torch
 
     from .VisualOdometryPipeLine import VisualOdometryPipeLine
     preset = dataset.replace("synthetic-", "")
     options, boot, ref_last = Op.get(preset)
+    if lk_fb_threshold is not None:
+        options["lk_fb_threshold"] = float(lk_fb_threshold)
     last = int(last_frame if last_frame is not None else ref_last)
     dev = torch.device(device or "cuda")
     if dataset.startswith("synthetic-"):
@@ -139,10 +144,13 @@ def main():
     ap.add_argument("--plot-every", type=int, default=0, help="also redraw every N frames (0: final only)")
     ap.add_argument("--poses", default=None, help="write the trajectory as KITTI pose rows")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--lk-fb-threshold", type=float, default=None, metavar="PX",
+                    help="keep a tracked point only if LK back to the previous frame returns within PX pixels")
     a = ap.parse_args()
     if not a.dataset.startswith("synthetic-") and not a.path:
         ap.error("--path is required for a dataset on disk")
-    res = run(a.dataset, a.path, a.last_frame, a.plot or None, a.plot_every, a.poses, verbose=a.verbose)
+    res = run(a.dataset, a.path, a.last_frame, a.plot or None, a.plot_every, a.poses, verbose=a.verbose,
+              lk_fb_threshold=a.lk_fb_threshold)
     print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
 
 
