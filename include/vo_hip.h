@@ -254,6 +254,31 @@ int vo_pnp_ransac(const vo_opts* o, int B, const float* obj, const float* img,
                   int32_t* success, uint8_t* inl_mask, int32_t* n_inl, double* work,
                   int64_t work_stride, vo_stream_t stream);
 
+/* Levenberg-Marquardt refinement of a pose on the reprojection error of its inliers, in the form
+ * of cv2.solvePnPRefineLM (rvec, tvec in and out); the project's own definition (the
+ * NumPy restatement tests/test_pnp_refine_ref.py), reproduced bit for bit.  obj [B][cap][3], img
+ * [B][cap][2] with counts[B]; mask [B][cap] selects the inliers (NULL = every point); success
+ * [B] (NULL = all): a chain with 0 is left untouched, info included.  max_iters 0..100, ftol finite
+ * and >= 0, else VO_EARG with nothing written.  info [B][4] (NULL = not wanted): iterations used,
+ * accepted steps, initial and final cost (sum of squared pixel residuals; +inf where the start
+ * pose has a point at z <= 0 or a cost that is not finite: pose unchanged, 0 iterations). */
+int vo_pnp_refine(const vo_opts* o, int B, const float* obj, const float* img, const uint8_t* mask,
+                  const int32_t* counts, int32_t cap, const int32_t* success, int32_t max_iters,
+                  double ftol, double* rvec, double* tvec, double* info, vo_stream_t stream);
+
+/* vo_pnp, vo_pnp_triangulate and vo_filter_pnp_triangulate with that refinement applied to every
+ * chain whose PnP succeeded, over its inliers, before anything reads the pose: pnp_rt, pose slot
+ * nF and the triangulation use the refined pose; the inlier mask, the counts and the statuses are
+ * those of the plain calls.  refine_iters = 0 is the plain call (the same launches); refine_info
+ * [B][4] or NULL as vo_pnp_refine's info (rows of chains that are not refined are not written). */
+int vo_pnp_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+              double refine_ftol, double* refine_info, vo_stream_t stream);
+int vo_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                          double refine_ftol, double* refine_info, vo_stream_t stream);
+int vo_filter_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s,
+                                 int32_t refine_iters, double refine_ftol, double* refine_info,
+                                 vo_stream_t stream);
+
 /* cv2.triangulatePoints (:188) for float32 points: P1,P2 [n][12] (row-major 3x4 each,
  * one pair per point), x1,x2 [n][2] -> out [n][4] float32. */
 int vo_triangulate_points(int n, const double* P1, const double* P2, const float* x1,

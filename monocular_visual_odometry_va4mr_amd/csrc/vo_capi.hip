@@ -3,7 +3,7 @@
 
 #include <string.h>
 
-extern "C" const char* vo_version(void) { return "vo_hip 0.2 (gfx950)"; }
+extern "C" const char* vo_version(void) { return "vo_hip 0.3 (gfx950)"; }
 
 extern "C" int vo_device_cus(void)
 {

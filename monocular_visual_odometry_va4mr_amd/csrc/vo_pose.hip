@@ -897,6 +897,316 @@ k_pnp_fused(PnPArgs A, vo_dims d, vo_state s)
     pnp_apply_block(d, s, A.rvec, A.tvec, A.success, A.mask);
 }
 
+// ------------------------------------------------------------------ LM refinement of the pose
+// Levenberg-Marquardt on the reprojection error over the inliers (the definition is
+// the NumPy restatement tests/test_pnp_refine_ref.py:refine_ref, matched operation by operation).
+// One 256-thread block per chain.  Lane t owns the inliers j = t, t + 256, ... and keeps their 28
+// sums (H's lower triangle by rows, g, c) in registers; a wave's lanes meet in the xor butterfly
+// (lane 0 holds p[l] += p[l + s], s = 32..1), the four waves in 4 x 28 doubles of LDS, summed
+// (q0 + q1) + (q2 + q3).  Thread 0 solves, retracts and tells the block what to do next through
+// RefShared::cmd, so every branch is block-uniform.
+#define REF_NS 28
+#define REF_STOP 0
+#define REF_EVAL 1
+#define REF_SKIP 2
+
+struct RefArgs {
+    int max_iters;          // 1..100 (0 never reaches a kernel)
+    double ftol;
+    double* info;           // [B][4] (iterations, accepted steps, initial c, final c) or NULL
+};
+
+struct RefShared {
+    double part[4][REF_NS];
+    double cur[REF_NS];     // sums at the accepted pose
+    double pose[12], trial[12];   // R row-major, t
+    int wbad[4];
+    int cmd;
+};
+
+VO_DEV bool ref_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// one inlier's terms at pose P added to the lane's sums
+VO_DEV void ref_accum(double* acc, bool& bad, const double* P, const CamK& k, double X0, double X1, double X2,
+                      double u, double v)
+{
+    const double x = ((P[0] * X0 + P[1] * X1) + P[2] * X2) + P[9];
+    const double y = ((P[3] * X0 + P[4] * X1) + P[5] * X2) + P[10];
+    const double z = ((P[6] * X0 + P[7] * X1) + P[8] * X2) + P[11];
+    if (!(z > 0.0)) bad = true;
+    const double iz = 1.0 / z;
+    const double rx = ((k.fx * x) * iz + k.cx) - u;
+    const double ry = ((k.fy * y) * iz + k.cy) - v;
+    const double a = k.fx * iz, b = k.fy * iz;
+    const double c = -((a * x) * iz), d = -((b * y) * iz);
+    // rows of the 2 x 6 Jacobian for Xc <- E(w) Xc + nu, columns nu then w (dXc/dw = -[Xc]x)
+    const double Ju[6] = {a, 0.0, c, c * y, a * z - c * x, -(a * y)};
+    const double Jv[6] = {0.0, b, d, d * y - b * z, -(d * x), b * x};
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) acc[q++] += Ju[i] * Ju[j] + Jv[i] * Jv[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += Ju[i] * rx + Jv[i] * ry;
+    acc[27] += rx * rx + ry * ry;
+}
+
+// The 28 sums at pose P (LDS) into S.part / S.wbad; ends with a block barrier.  MASKED: the
+// inliers are the points with mask[i] != 0; their ranks come from a block scan per 256 points and
+// their indices pass through a 512-entry LDS ring, so that lane t still takes ranks t, t + 256, ...
+template <bool MASKED>
+VO_DEV void ref_eval(RefShared& S, const double* P, const CamK& k, const float* obj, const float* img,
+                     const uint8_t* mask, int n)
+{
+    const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
+    double acc[REF_NS], Pr[12];
+#pragma unroll
+    for (int q = 0; q < REF_NS; ++q) acc[q] = 0.0;
+    for (int q = 0; q < 12; ++q) Pr[q] = P[q];
+    bool bad = false;
+    if constexpr (!MASKED) {
+        for (int i = tid; i < n; i += 256)
+            ref_accum(acc, bad, Pr, k, obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], img[2 * i], img[2 * i + 1]);
+    } else {
+        __shared__ int ring[512];
+        __shared__ int lds16[16];
+        int filled = 0, used = 0;           // ranks produced / consumed (used is a multiple of 256)
+        for (int base = 0; base < n; base += 256) {
+            const int i = base + tid;
+            const bool in = i < n && mask[i] != 0;
+            int tot;
+            const int pos = filled + block_scan_flag(in, lds16, &tot);   // its barriers order the ring's reuse
+            if (in) ring[pos & 511] = i;
+            filled += tot;
+            __syncthreads();
+            if (filled - used >= 256) {
+                const int i2 = ring[(used + tid) & 511];
+                ref_accum(acc, bad, Pr, k, obj[3 * i2], obj[3 * i2 + 1], obj[3 * i2 + 2], img[2 * i2], img[2 * i2 + 1]);
+                used += 256;
+            }
+        }
+        if (tid < filled - used) {
+            const int i2 = ring[(used + tid) & 511];
+            ref_accum(acc, bad, Pr, k, obj[3 * i2], obj[3 * i2 + 1], obj[3 * i2 + 2], img[2 * i2], img[2 * i2 + 1]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < REF_NS; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+        if (lane == 0) S.part[w][q] = v;
+    }
+    const bool wb = __ballot(bad) != 0ull;
+    if (lane == 0) S.wbad[w] = wb ? 1 : 0;
+    __syncthreads();
+}
+
+// thread 0: the block's sums into out; false (the evaluation fails) if a point had z <= 0 or c is not finite
+VO_DEV bool ref_total(const RefShared& S, double* out)
+{
+    for (int q = 0; q < REF_NS; ++q) out[q] = (S.part[0][q] + S.part[1][q]) + (S.part[2][q] + S.part[3][q]);
+    const bool bad = (S.wbad[0] | S.wbad[1] | S.wbad[2] | S.wbad[3]) != 0;
+    return !bad && ref_finite(out[27]);
+}
+
+// thread 0: (H + lam diag H) d = -g by a 6 x 6 Cholesky (lower triangle, column by column)
+VO_DEV bool ref_solve(const double* cur, double lam, double* d)
+{
+    double L[6][6], y[6];
+    for (int j = 0; j < 6; ++j) {
+        const double h = cur[j * (j + 1) / 2 + j];
+        double s = h + lam * h;
+        for (int q = 0; q < j; ++q) s = s - L[j][q] * L[j][q];
+        if (!(s > 0.0) || !ref_finite(s)) return false;
+        L[j][j] = sqrt(s);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = cur[i * (i + 1) / 2 + j];
+            for (int q = 0; q < j; ++q) v = v - L[i][q] * L[j][q];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        double v = -cur[21 + i];
+        for (int q = 0; q < i; ++q) v = v - L[i][q] * y[q];
+        y[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int q = i + 1; q < 6; ++q) v = v - L[q][i] * d[q];
+        d[i] = v / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!ref_finite(d[i])) return false;
+    return true;
+}
+
+// thread 0: trial = (E R, E t + nu), E the rotation of the normalised quaternion (1, w / 2)
+VO_DEV void ref_retract(const double* P, const double* d, double* T)
+{
+    const double qx = d[3] * 0.5, qy = d[4] * 0.5, qz = d[5] * 0.5;
+    const double inv = 1.0 / sqrt(((1.0 + qx * qx) + qy * qy) + qz * qz);
+    const double w = inv, x = qx * inv, y = qy * inv, z = qz * inv;
+    const double E[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                         2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                         2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j)
+            T[3 * i + j] = (E[3 * i] * P[j] + E[3 * i + 1] * P[3 + j]) + E[3 * i + 2] * P[6 + j];
+        T[9 + i] = ((E[3 * i] * P[9] + E[3 * i + 1] * P[10]) + E[3 * i + 2] * P[11]) + d[i];
+    }
+}
+
+// The whole refinement of one chain by its block: rvec / tvec (3 doubles each) in and out, info
+// (4 doubles) or NULL.  Every thread of the block must call it.
+template <bool MASKED>
+VO_DEV void pnp_refine_block(const double* K, const float* obj, const float* img, const uint8_t* mask, int n,
+                             int max_iters, double ftol, double* rvec, double* tvec, double* info)
+{
+    __shared__ RefShared S;
+    const int tid = threadIdx.x;
+    const CamK k = camk(K);
+    const double inf = __builtin_huge_val();
+    if (tid == 0) {
+        rodrigues_v2m(rvec, S.pose);
+        for (int q = 0; q < 3; ++q) S.pose[9 + q] = tvec[q];
+    }
+    __syncthreads();
+    ref_eval<MASKED>(S, S.pose, k, obj, img, mask, n);
+    // thread 0's state
+    double lam = 1e-3, c = inf, c0 = inf;
+    int it = 0, nacc = 0;
+    // thread 0: the head of an iteration -- solve and retract, or skip / stop on a failed solve
+    auto prepare = [&]() {
+        if (it >= max_iters) { S.cmd = REF_STOP; return; }
+        ++it;
+        double d[6];
+        if (!ref_solve(S.cur, lam, d)) {
+            lam = lam * 10.0;
+            S.cmd = lam > 1e12 ? REF_STOP : REF_SKIP;
+        } else {
+            ref_retract(S.pose, d, S.trial);
+            S.cmd = REF_EVAL;
+        }
+    };
+    if (tid == 0) {
+        const bool ok = ref_total(S, S.cur);
+        if (ok) {
+            c = c0 = S.cur[27];
+            prepare();
+        } else {
+            // pose unchanged, 0 iterations
+            S.cmd = REF_STOP;
+            it = -1;
+        }
+    }
+    while (true) {
+        __syncthreads();
+        const int cmd = S.cmd;
+        __syncthreads();
+        if (cmd == REF_STOP) break;
+        if (cmd == REF_EVAL) {
+            ref_eval<MASKED>(S, S.trial, k, obj, img, mask, n);
+            if (tid == 0) {
+                double nw[REF_NS];
+                const bool ok = ref_total(S, nw);
+                const double c1 = ok ? nw[27] : inf;
+                const bool conv = fabs(c - c1) <= ftol * c;
+                bool stop = conv;
+                if (c1 < c) {
+                    for (int q = 0; q < REF_NS; ++q) S.cur[q] = nw[q];
+                    for (int q = 0; q < 12; ++q) S.pose[q] = S.trial[q];
+                    c = c1;
+                    lam = lam / 10.0;
+                    if (!(lam > 1e-12)) lam = 1e-12;
+                    ++nacc;
+                } else {
+                    lam = lam * 10.0;
+                    if (lam > 1e12) stop = true;
+                }
+                if (stop) S.cmd = REF_STOP;
+                else prepare();
+            }
+        } else if (tid == 0) {
+            prepare();
+        }
+    }
+    if (tid == 0) {
+        if (it >= 0) {
+            double rv[3];
+            rodrigues_m2v(S.pose, rv);
+            for (int q = 0; q < 3; ++q) { rvec[q] = rv[q]; tvec[q] = S.pose[9 + q]; }
+        } else {
+            it = 0;
+        }
+        if (info) { info[0] = (double)it; info[1] = (double)nacc; info[2] = c0; info[3] = c; }
+    }
+}
+
+// The engine's refinement, after pnp_apply_block / pnp_apply_split and a block barrier: the chain's
+// inliers are then its landmarks lm_X / lm_kp[0..nInl) in ascending order.  Refines pnp_rt and
+// writes pose slot nF again (the same expressions as pnp_apply_block).  A chain whose status is
+// not 0 here (too few points, PnP failed, capacity) is left alone; nothing below writes a status.
+VO_DEV void pnp_refine_state(const PnPArgs& A, const vo_dims& d, const vo_state& s, const RefArgs& Rf)
+{
+    const int b = blockIdx.x;
+    if (s.status[b] != 0) return;
+    PNPPROF(30);
+    double* rvec = A.rvec + 3 * b;
+    double* tvec = A.tvec + 3 * b;
+    pnp_refine_block<false>(A.K, s.lm_X + (int64_t)b * d.ncap * 3, s.lm_kp + (int64_t)b * d.ncap * 2, nullptr, s.nInl[b],
+                            Rf.max_iters, Rf.ftol, rvec, tvec, Rf.info ? Rf.info + 4 * b : nullptr);
+    if (threadIdx.x == 0) {
+        double Rwc[9];
+        rodrigues_v2m(rvec, Rwc);
+        const int f = s.nF[b];                       // < fcap: the status is 0
+        double* Rcw = s.pose_R + ((int64_t)b * d.fcap + f) * 9;
+        double* tcw = s.pose_t + ((int64_t)b * d.fcap + f) * 3;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rcw[i * 3 + j] = Rwc[j * 3 + i];
+        for (int i = 0; i < 3; ++i)
+            tcw[i] = __builtin_fma(-Rcw[i * 3 + 2], tvec[2], __builtin_fma(-Rcw[i * 3 + 1], tvec[1], -Rcw[i * 3] * tvec[0]));
+    }
+    PNPPROF(31);
+}
+
+struct RefineArgs {
+    double K[9];
+    const float* obj;       // [B][cap][3]
+    const float* img;       // [B][cap][2]
+    const uint8_t* mask;    // [B][cap] or NULL
+    const int32_t* counts;
+    int cap;
+    const int32_t* success; // [B] or NULL
+    double* rvec;           // [B][3]
+    double* tvec;           // [B][3]
+    RefArgs ref;
+};
+
+// vo_pnp_refine
+__global__ void __launch_bounds__(256) k_pnp_refine(RefineArgs A)
+{
+    const int b = blockIdx.x;
+    if (A.success && A.success[b] == 0) return;
+    int n = A.counts[b];
+    n = n < 0 ? 0 : n > A.cap ? A.cap : n;
+    const float* obj = A.obj + (int64_t)b * A.cap * 3;
+    const float* img = A.img + (int64_t)b * A.cap * 2;
+    double* info = A.ref.info ? A.ref.info + 4 * b : nullptr;
+    if (A.mask)
+        pnp_refine_block<true>(A.K, obj, img, A.mask + (int64_t)b * A.cap, n, A.ref.max_iters, A.ref.ftol,
+                               A.rvec + 3 * b, A.tvec + 3 * b, info);
+    else
+        pnp_refine_block<false>(A.K, obj, img, nullptr, n, A.ref.max_iters, A.ref.ftol, A.rvec + 3 * b, A.tvec + 3 * b, info);
+}
+
+// the engine's refinement as a launch of its own, after vo_pnp's (the unfused step form)
+__global__ void __launch_bounds__(256) k_pnp_refine_state(PnPArgs A, vo_dims d, vo_state s, RefArgs Rf)
+{
+    pnp_refine_state(A, d, s, Rf);
+}
+
 // ------------------------------------------------------------------ triangulation
 // The reference forms its projection matrices and camera-frame depths with numpy
 // matmuls (VisualOdometryPipeLine.py:74-75 invert_transform, :157-168, :170-171), which
@@ -1199,6 +1509,30 @@ k_pnp_tri(PnPArgs A, TriArgs T)
     pnp_ransac_block(A, defer, &pend);
     __syncthreads();
     pnp_apply_split(T.d, T.s, A.rvec, A.tvec, A.success, A.mask, defer, pend);
+    __syncthreads();
+    PNPPROF(14);
+    triangulate_block(T);
+    PNPPROF(15);
+}
+
+// k_pnp_tri with the LM refinement between the epilogue and the triangulation, which then reads
+// the refined pose slot.  A kernel of its own: k_pnp_tri is what runs with the option off.
+template <int WPE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
+k_pnp_tri_ref(PnPArgs A, TriArgs T, RefArgs Rf)
+{
+    if (T.compact) {
+        track_compact_block(T.d, T.s);
+        __syncthreads();
+    }
+    __shared__ double defer[12];
+    __shared__ int pend;
+    if (threadIdx.x == 0) pend = 0;
+    pnp_ransac_block(A, defer, &pend);
+    __syncthreads();
+    pnp_apply_split(T.d, T.s, A.rvec, A.tvec, A.success, A.mask, defer, pend);
+    __syncthreads();
+    pnp_refine_state(A, T.d, T.s, Rf);
     __syncthreads();
     PNPPROF(14);
     triangulate_block(T);
@@ -1512,10 +1846,18 @@ static void fill_pnp_engine(PnPArgs& P, const vo_dims* d, const vo_opts* o, cons
     P.success = s->pnp_ok; P.n_inl = s->pnp_ninl; P.mask = s->pnp_mask;
 }
 
-extern "C" int vo_pnp(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)
+// refine_iters 0..100 (0 = off), refine_ftol finite and >= 0
+static inline bool refine_args_ok(int32_t iters, double ftol)
+{
+    return iters >= 0 && iters <= 100 && ftol >= 0.0 && ftol <= 1.7976931348623157e308;
+}
+
+extern "C" int vo_pnp_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters, double refine_ftol,
+                         double* refine_info, vo_stream_t stream)
 {
     if (!d || !o || !s) return VO_EARG;
     if (d->work_stride < 12LL * d->ncap + 64) return VO_EARG;
+    if (!refine_args_ok(refine_iters, refine_ftol)) return VO_EARG;
     PnPArgs P;
     fill_pnp_engine(P, d, o, s);
     hipStream_t st = VO_STREAM(stream);
@@ -1529,6 +1871,31 @@ extern "C" int vo_pnp(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_
     } else {
         hipLaunchKernelGGL(k_pnp_fused<1>, dim3(d->B), dim3(256), 0, st, P, *d, *s);
     }
+    if (refine_iters > 0) {
+        // the unfused form is off the latency path: the refinement is a launch of its own
+        RefArgs Rf = {refine_iters, refine_ftol, refine_info};
+        hipLaunchKernelGGL(k_pnp_refine_state, dim3(d->B), dim3(256), 0, st, P, *d, *s, Rf);
+    }
+    return hip_rc();
+}
+
+extern "C" int vo_pnp(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)
+{
+    return vo_pnp_ex(d, o, s, 0, 0.0, nullptr, stream);
+}
+
+extern "C" int vo_pnp_refine(const vo_opts* o, int B, const float* obj, const float* img, const uint8_t* mask,
+                             const int32_t* counts, int32_t cap, const int32_t* success, int32_t max_iters, double ftol,
+                             double* rvec, double* tvec, double* info, vo_stream_t stream)
+{
+    if (!o || B < 1 || !obj || !img || !counts || cap < 0 || !rvec || !tvec) return VO_EARG;
+    if (!refine_args_ok(max_iters, ftol)) return VO_EARG;
+    RefineArgs A;
+    for (int i = 0; i < 9; ++i) A.K[i] = o->K[i];
+    A.obj = obj; A.img = img; A.mask = mask; A.counts = counts; A.cap = cap; A.success = success;
+    A.rvec = rvec; A.tvec = tvec;
+    A.ref.max_iters = max_iters; A.ref.ftol = ftol; A.ref.info = info;
+    hipLaunchKernelGGL(k_pnp_refine, dim3(B), dim3(256), 0, VO_STREAM(stream), A);
     return hip_rc();
 }
 
@@ -1563,10 +1930,12 @@ extern "C" int vo_triangulate(const vo_dims* d, const vo_opts* o, const vo_state
     return hip_rc();
 }
 
-static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s, int compact, vo_stream_t stream)
+static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s, int compact, int32_t refine_iters,
+                          double refine_ftol, double* refine_info, vo_stream_t stream)
 {
     if (!d || !o || !s) return VO_EARG;
     if (d->work_stride < 12LL * d->ncap + 64) return VO_EARG;
+    if (!refine_args_ok(refine_iters, refine_ftol)) return VO_EARG;
     PnPArgs P;
     fill_pnp_engine(P, d, o, s);
     TriArgs T;
@@ -1578,19 +1947,37 @@ static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s,
     static const int force = [] { const char* e = getenv("VO_PNP_TRI_WPE"); return e ? atoi(e) : 0; }();
     const int n_cu = device_cus() > 0 ? device_cus() : 256;      // of the current device
     const bool two = force ? force == 2 : d->B > n_cu;
+    if (refine_iters > 0) {
+        RefArgs Rf = {refine_iters, refine_ftol, refine_info};
+        if (two) hipLaunchKernelGGL(k_pnp_tri_ref<VO_PNP_WPE>, dim3(d->B), dim3(256), 0, VO_STREAM(stream), P, T, Rf);
+        else hipLaunchKernelGGL(k_pnp_tri_ref<1>, dim3(d->B), dim3(256), 0, VO_STREAM(stream), P, T, Rf);
+        return hip_rc();
+    }
     if (two) hipLaunchKernelGGL(k_pnp_tri<VO_PNP_WPE>, dim3(d->B), dim3(256), 0, VO_STREAM(stream), P, T);
     else hipLaunchKernelGGL(k_pnp_tri<1>, dim3(d->B), dim3(256), 0, VO_STREAM(stream), P, T);
     return hip_rc();
 }
 
+extern "C" int vo_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                                     double refine_ftol, double* refine_info, vo_stream_t stream)
+{
+    return launch_pnp_tri(d, o, s, 0, refine_iters, refine_ftol, refine_info, stream);
+}
+
+extern "C" int vo_filter_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                                            double refine_ftol, double* refine_info, vo_stream_t stream)
+{
+    return launch_pnp_tri(d, o, s, 1, refine_iters, refine_ftol, refine_info, stream);
+}
+
 extern "C" int vo_pnp_triangulate(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)
 {
-    return launch_pnp_tri(d, o, s, 0, stream);
+    return vo_pnp_triangulate_ex(d, o, s, 0, 0.0, nullptr, stream);
 }
 
 extern "C" int vo_filter_pnp_triangulate(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)
 {
-    return launch_pnp_tri(d, o, s, 1, stream);
+    return vo_filter_pnp_triangulate_ex(d, o, s, 0, 0.0, nullptr, stream);
 }
 
 extern "C" int vo_add_corners_finish(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)

@@ -199,6 +199,40 @@ def solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec=Non
     return True, rv.cpu().numpy().reshape(3, 1), tv.cpu().numpy().reshape(3, 1), inl
 
 
+FLT_EPSILON = 1.1920928955078125e-07
+
+
+def solvePnPRefineLM(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec, tvec,
+                     criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 20, FLT_EPSILON)):
+    """cv2.solvePnPRefineLM's form over vo_pnp_refine: Levenberg-Marquardt on the reprojection
+    error from (rvec, tvec); returns the refined (rvec, tvec) as 3x1 float64 and leaves its inputs
+    alone.  The iteration is this project's own, not OpenCV's LMSolver: criteria's
+    count is the iteration limit (100 without the COUNT bit), its epsilon the relative cost
+    tolerance (0 without the EPS bit)."""
+    if distCoeffs is not None and np.any(np.asarray(distCoeffs) != 0):
+        raise NotImplementedError("non-zero distortion")
+    obj = np.ascontiguousarray(np.asarray(objectPoints, np.float32).reshape(-1, 3))
+    img = np.ascontiguousarray(np.asarray(imagePoints, np.float32).reshape(-1, 2))
+    n = obj.shape[0]
+    if img.shape[0] != n:
+        raise error("solvePnPRefineLM: npoints == ipoints required")
+    ctype, count, eps = criteria
+    max_iters = int(count) if int(ctype) & TERM_CRITERIA_COUNT else 100
+    ftol = float(eps) if int(ctype) & TERM_CRITERIA_EPS else 0.0
+    if not 0 <= max_iters <= 100 or not (math.isfinite(ftol) and ftol >= 0):
+        raise error("solvePnPRefineLM: criteria must give 0..100 iterations and a finite epsilon >= 0")
+    o = make_opts(np.asarray(cameraMatrix, np.float64), dict(_DEFAULT_OPTS))
+    dev = _dev()
+    d_obj = torch.from_numpy(obj).to(dev)
+    d_img = torch.from_numpy(img).to(dev)
+    cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+    rv = torch.from_numpy(np.array(rvec, np.float64).reshape(3)).to(dev)       # copies: the inputs stay
+    tv = torch.from_numpy(np.array(tvec, np.float64).reshape(3)).to(dev)
+    L.check(L.lib().vo_pnp_refine(C.byref(o), 1, _p(d_obj), _p(d_img), None, _p(cnt), n, None, max_iters,
+                                  C.c_double(ftol), _p(rv), _p(tv), None, _stream()), "vo_pnp_refine")
+    return rv.cpu().numpy().reshape(3, 1), tv.cpu().numpy().reshape(3, 1)
+
+
 # ---------------------------------------------------------------- DLT (:188)
 def triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2):
     x1 = np.asarray(projPoints1)

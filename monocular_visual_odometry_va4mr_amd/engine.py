@@ -106,6 +106,22 @@ def make_opts(K: np.ndarray, options: dict) -> L.VoOpts:
     return o
 
 
+def parse_refine(options: dict) -> tuple[int, float]:
+    """(pnp_refine_iters, pnp_refine_ftol) of an options dict, validated: iterations an integer in
+    0..100 (absent / None = 0 = off), the tolerance finite and >= 0 (default 1e-10)."""
+    it = options.get("pnp_refine_iters")
+    if it is None:
+        it = 0
+    if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or not 0 <= int(it) <= 100:
+        raise ValueError("pnp_refine_iters must be an integer in 0..100 (or None)")
+    ftol = options.get("pnp_refine_ftol")
+    ftol = 1e-10 if ftol is None else ftol
+    if isinstance(ftol, bool) or not isinstance(ftol, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(ftol) and ftol >= 0):
+        raise ValueError("pnp_refine_ftol must be a finite number >= 0")
+    return int(it), float(ftol)
+
+
 class Engine:
     """B chains of the VO per-frame step on one device."""
 
@@ -195,6 +211,11 @@ class Engine:
             if not (self.lk_fb_threshold > 0 and math.isfinite(self.lk_fb_threshold)):
                 raise ValueError("lk_fb_threshold must be a positive finite number of pixels (or None)")
             self._fb_scratch = z(B, ncap + pcap, 2, dt=torch.float32)      # the points tracked back
+        # pnp_refine_iters (this build's own key, absent / None / 0 = off): Levenberg-Marquardt on the
+        # inliers' reprojection error after solvePnPRansac, at most that many iterations;
+        # pnp_refine_ftol: its relative cost tolerance
+        self.pnp_refine_iters, self.pnp_refine_ftol = parse_refine(options)
+        self._refine_info = z(B, 4, dt=torch.float64) if self.pnp_refine_iters else None
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -214,6 +235,14 @@ class Engine:
 
     def statuses(self) -> np.ndarray:
         return self.t["status"].cpu().numpy()
+
+    def refine_info(self):
+        """[B][4] float64 of the last step's pose refinement (iterations used, accepted steps,
+        initial and final cost) for the chains it ran on, or None with pnp_refine_iters off (no
+        buffer exists then).  Synchronises."""
+        if self._refine_info is None:
+            return None
+        return self._refine_info.cpu().numpy()
 
     def _sw_alloc(self):
         if getattr(self, "_sw_host", None) is None:
@@ -407,7 +436,18 @@ class Engine:
             lat = self._latency_stream()
             lat.wait_stream(main)                                 # tracking done
         sl = C.c_void_p(lat.cuda_stream)
-        if fused:
+        if self.pnp_refine_iters:
+            # the same launches through the _ex entry points, the pose refined inside them
+            rit, rtol = self.pnp_refine_iters, C.c_double(self.pnp_refine_ftol)
+            rinfo = C.c_void_p(self._refine_info.data_ptr())
+            if fused:
+                pnp = lib.vo_filter_pnp_triangulate_ex if defer else lib.vo_pnp_triangulate_ex
+                run(2, lat, lambda: pnp(pd, po, ps, rit, rtol, rinfo, sl))
+                run(3, lat, lambda: 0)
+            else:
+                run(2, lat, lambda: lib.vo_pnp_ex(pd, po, ps, rit, rtol, rinfo, sl))
+                run(3, lat, lambda: lib.vo_triangulate(pd, po, ps, 0, sl))
+        elif fused:
             # one launch for filtering, PnP and triangulation (vo_filter_pnp_triangulate); stage 3
             # is then empty
             pnp = lib.vo_filter_pnp_triangulate if defer else lib.vo_pnp_triangulate

@@ -56,11 +56,13 @@ def dataset_frames(dataset: str, path: str):
 
 def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str | None = "out/interface_plot.png",
         plot_every: int = 0, poses_out: str | None = None, device=None, verbose: bool = False, K=None,
-        lk_fb_threshold: float | None = None) -> dict:
+        lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
+        pnp_refine_ftol: float | None = None) -> dict:
     """Run main.py's loop; returns a summary dict and (in "_vo") the pipeline object.
     K overrides the dataset's intrinsics (e.g. for a synthetic sequence written to disk).
     ``lk_fb_threshold`` (pixels): the engine's forward-backward gate on tracked points; None
-    (the reference's behaviour) leaves it off."""
+    (the reference's behaviour) leaves it off.  ``pnp_refine_iters`` / ``pnp_refine_ftol``: the
+    engine's Levenberg-Marquardt refinement of every PnP pose (None or 0 = off)."""
     import torch
 
     from .VisualOdometryPipeLine import VisualOdometryPipeLine
@@ -68,6 +70,10 @@ def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str
     options, boot, ref_last = Op.get(preset)
     if lk_fb_threshold is not None:
         options["lk_fb_threshold"] = float(lk_fb_threshold)
+    if pnp_refine_iters is not None:
+        options["pnp_refine_iters"] = pnp_refine_iters
+    if pnp_refine_ftol is not None:
+        options["pnp_refine_ftol"] = pnp_refine_ftol
     last = int(last_frame if last_frame is not None else ref_last)
     dev = torch.device(device or "cuda")
     if dataset.startswith("synthetic-"):
@@ -146,11 +152,16 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--lk-fb-threshold", type=float, default=None, metavar="PX",
                     help="keep a tracked point only if LK back to the previous frame returns within PX pixels")
+    ap.add_argument("--pnp-refine-iters", type=int, default=None, metavar="N",
+                    help="refine every PnP pose by at most N Levenberg-Marquardt iterations on the inliers (0 = off)")
+    ap.add_argument("--pnp-refine-ftol", type=float, default=None, metavar="X",
+                    help="relative cost tolerance of that refinement (default 1e-10)")
     a = ap.parse_args()
     if not a.dataset.startswith("synthetic-") and not a.path:
         ap.error("--path is required for a dataset on disk")
     res = run(a.dataset, a.path, a.last_frame, a.plot or None, a.plot_every, a.poses, verbose=a.verbose,
-              lk_fb_threshold=a.lk_fb_threshold)
+              lk_fb_threshold=a.lk_fb_threshold, pnp_refine_iters=a.pnp_refine_iters,
+              pnp_refine_ftol=a.pnp_refine_ftol)
     print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
 
 

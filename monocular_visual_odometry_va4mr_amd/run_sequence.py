@@ -54,7 +54,8 @@ def default_groups(chains: int) -> int:
 def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, seed: int = 1, device=None,
         rank: int = 0, world: int = 1, out_path: str | None = None, engine_cls=None, renderer=None,
         reference: dict | None = None, prerender: bool = True, time_boot: bool = True,
-        groups: int | None = None, lk_fb_threshold: float | None = None) -> dict | None:
+        groups: int | None = None, lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
+        pnp_refine_ftol: float | None = None) -> dict | None:
     """Run the plan; rank 0 returns the report (None on other ranks).
 
     ``engine_cls`` / ``renderer`` default to engine.Engine and synth.Renderer (tests pass
@@ -82,6 +83,10 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
     opts, (b0, b1), _ = Op.get(preset)
     if lk_fb_threshold is not None:         # the engine's forward-backward gate (pixels); None = off
         opts["lk_fb_threshold"] = float(lk_fb_threshold)
+    if pnp_refine_iters is not None:        # the engine's LM refinement of every PnP pose; None / 0 = off
+        opts["pnp_refine_iters"] = pnp_refine_iters
+    if pnp_refine_ftol is not None:
+        opts["pnp_refine_ftol"] = pnp_refine_ftol
     gap = b1 - b0
     plan = Sh.plan_shards(n_frames, world * shards_per_rank, gap, overlap)
     mine = Sh.rank_shards(plan, rank, world)
@@ -344,6 +349,10 @@ def main():
     ap.add_argument("--out", default=None, help="write the stitched positions (frame segment x y z)")
     ap.add_argument("--lk-fb-threshold", type=float, default=None, metavar="PX",
                     help="keep a tracked point only if LK back to the previous frame returns within PX pixels")
+    ap.add_argument("--pnp-refine-iters", type=int, default=None, metavar="N",
+                    help="refine every PnP pose by at most N Levenberg-Marquardt iterations on the inliers (0 = off)")
+    ap.add_argument("--pnp-refine-ftol", type=float, default=None, metavar="X",
+                    help="relative cost tolerance of that refinement (default 1e-10)")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -355,7 +364,8 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
     ref = reference_shards(args.reference, world * args.shards_per_gpu) if args.reference else None
     res = run(args.preset, args.frames, args.shards_per_gpu, args.overlap, args.seed, dev, rank, world, args.out,
-              reference=ref, lk_fb_threshold=args.lk_fb_threshold)
+              reference=ref, lk_fb_threshold=args.lk_fb_threshold, pnp_refine_iters=args.pnp_refine_iters,
+              pnp_refine_ftol=args.pnp_refine_ftol)
     if res is not None:
         print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
     if world > 1:
