@@ -348,14 +348,21 @@ int vo_bf_knn2_batch(int B, const float* q, const int32_t* nq, int32_t qcap, con
                      void* scratch, int64_t scratch_bytes, vo_stream_t stream);
 
 /* Ratio test + match gathering of initial_feature_matching (:218-245) for B chains:
- * keeps query i iff dist0 < ratio * dist1 (in double, as Python), in query order. */
+ * keeps query i iff both neighbours exist (idx >= 0) and dist0 < ratio * dist1 (in double, as
+ * Python; a tie is dropped), in query order.  pts0 / pts1 are [B][cap][2]; counts[b] is the number
+ * of matches that passed.  Overflow is reported, not truncated: where more than cap pass, counts[b]
+ * is that larger number, the first cap matches are stored and no row at or past cap is written.
+ * vo_bootstrap ends a chain whose count exceeds its cap with VO_ST_CAPACITY, and
+ * vo_find_essential gives ok = 0 for it without reading its points. */
 int vo_ratio_matches(int B, const float* kp0, const float* kp1, int32_t kp_stride,
                      const int32_t* idx2, const float* dist2, const int32_t* nq, int32_t q_stride,
                      double ratio, float* pts0, float* pts1, int32_t* counts, int32_t cap,
                      vo_stream_t stream);
 
 /* cv2.findEssentialMat(p0,p1,K,RANSAC,prob,threshold) (:308) for B problems of
- * [B][cap] points with counts; E [B][9], mask [B][cap]. */
+ * [B][cap] points with counts; E [B][9], mask [B][cap]; work: work_doubles >= 4 cap + 90 * 64 per
+ * problem.  counts[b] < 5: ok = 0, mask[:counts[b]] = 0, E untouched.  counts[b] > cap (the
+ * overflow vo_ratio_matches reports): ok = 0, nothing else read or written. */
 int vo_find_essential(const vo_opts* o, int B, const float* p0, const float* p1,
                       const int32_t* counts, int32_t cap, double prob, double threshold,
                       int32_t max_iters, double* E, uint8_t* mask, int32_t* ok, double* work,
@@ -368,7 +375,10 @@ int vo_recover_pose(const vo_opts* o, int B, const double* E, const float* p0,
 
 /* Bootstrap assembly into chain state (initial_feature_matching + :308-323): from the
  * per-chain bootstrap matches (pts0/pts1 [B][cap], counts) run E-RANSAC, inlier
- * filtering, recoverPose, sign fix, triangulation, pose append, num_pts. */
+ * filtering, recoverPose, sign fix, triangulation, pose append, num_pts.  Per chain: counts[b] = 0
+ * -> VO_ST_NO_MATCHES; counts[b] > cap (vo_ratio_matches' overflow) or more matches than pcap ->
+ * VO_ST_CAPACITY; no essential matrix -> VO_ST_ESSENTIAL_FAILED.  Such a chain keeps
+ * transforms = [(I, 0)] (nF = 1) with no landmarks and no candidates. */
 int vo_bootstrap(const vo_dims* d, const vo_opts* o, const vo_state* s, const float* pts0,
                  const float* pts1, const int32_t* counts, int32_t cap, vo_stream_t stream);
 

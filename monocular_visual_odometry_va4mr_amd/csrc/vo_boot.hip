@@ -478,6 +478,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8
     const int b = blockIdx.x, tid = threadIdx.x;
     if (A.chain_status && A.chain_status[b] != 0) return;
     const int n = A.counts[b];
+    // more matches than rows (vo_ratio_matches reports the count it could not store): no model, and
+    // nothing beyond the chain's cap rows is read or written; k_boot_apply sets VO_ST_CAPACITY
+    if (n > A.cap) {
+        if (tid == 0) A.ok[b] = 0;
+        return;
+    }
     const float* p0 = A.p0 + (int64_t)b * A.cap * 2;
     const float* p1 = A.p1 + (int64_t)b * A.cap * 2;
     uint8_t* mask = A.mask + (int64_t)b * A.cap;
@@ -785,6 +791,7 @@ __global__ void __launch_bounds__(256) k_boot_apply(vo_dims d, vo_state s, const
         for (int q = 0; q < 9; ++q) R0[q] = (q % 4 == 0) ? 1.0 : 0.0;       // transforms[0] = (I, 0)
         for (int q = 0; q < 3; ++q) t0[q] = 0.0;
         if (n == 0) s.status[b] = VO_ST_NO_MATCHES;
+        else if (n > cap) s.status[b] = VO_ST_CAPACITY;                // more matches than pts0 / pts1 hold
         else if (!eok[b]) s.status[b] = VO_ST_ESSENTIAL_FAILED;
         else if (n > d.pcap) s.status[b] = VO_ST_CAPACITY;
     }

@@ -1366,7 +1366,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
     }
 }
 
-// ratio test + gathering (:218-245), ordered by query index
+// ratio test + gathering (:218-245), ordered by query index.  counts[b] is the number of matches
+// that pass, also when it exceeds cap (only the first cap are stored): the overflow is reported,
+// not truncated, and vo_bootstrap ends such a chain with VO_ST_CAPACITY
 __global__ void __launch_bounds__(256) k_ratio(const float* kp0, const float* kp1, int kps, const int32_t* idx2,
                                               const float* dist2, const int32_t* nq_p, int qs, double ratio,
                                               float* pts0, float* pts1, int32_t* counts, int cap)
@@ -1395,7 +1397,7 @@ __global__ void __launch_bounds__(256) k_ratio(const float* kp0, const float* kp
         }
         out += tot;
     }
-    if (tid == 0) counts[b] = out < cap ? out : cap;
+    if (tid == 0) counts[b] = out;
 }
 
 }  // namespace

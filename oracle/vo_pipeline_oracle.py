@@ -188,6 +188,33 @@ def initialize(s: OracleState, img0, img1):
     s.prev_img = img1
 
 
+def initialize_from_matches(s: OracleState, p0, p1, img1):
+    """initialization :293-323 from given bootstrap matches (p0, p1 float32 (n, 2), what
+    initial_feature_matching gathers from the ratio test) instead of SIFT + knnMatch: the statements
+    of bootstrap_matches after the match list (a fresh state, potential_frame None; the dead
+    descriptor state of quirk Q6 is not kept) followed by the rest of initialize, unchanged.  As in
+    the reference, no matches leave the candidate lists empty, and too few for an essential matrix
+    make recoverPose raise: the two cases the engine reports as VO_ST_NO_MATCHES and
+    VO_ST_ESSENTIAL_FAILED."""
+    p0 = np.float32(p0).reshape(-1, 2)
+    p1 = np.float32(p1).reshape(-1, 2)
+    if len(p0) > 0:
+        s.cand, s.cand_first = p1, p0
+        s.cand_tau = np.ones((len(p1), 1)) * (len(s.transforms) - 1)
+        s.cand_desc = np.zeros((len(p1), 0), np.float32)
+    E, m = cv.findEssentialMat(s.cand_first, s.cand, s.K, method=cv.RANSAC, prob=0.99, threshold=1)
+    inl = m.ravel() == 1
+    s.outl_pts = s.cand[~inl]
+    s.inl_pts = s.cand[inl]
+    _keep_cands(s, inl)
+    _, R, t, _ = cv.recoverPose(E, s.cand_first, s.cand, s.K)
+    t *= np.sign(t[2])                                                  # quirk Q2
+    triangulate_candidates(s, R, t)
+    s.transforms.append((R, t))
+    s.num_pts = [sum(inl)]
+    s.prev_img = img1
+
+
 def step(s: OracleState, img):
     """continuous_operation :326-373."""
     track(s, img)
