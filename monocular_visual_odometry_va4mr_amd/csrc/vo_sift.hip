@@ -1181,6 +1181,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
             cos_t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lane_cos), qi));
             sin_t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lane_sin), qi));
         } else {
+            // unreachable under kp_cap <= SORT_N = 32,768: a wave's 65th keypoint needs more than
+            // 64 * SIFT_WAVE_BLOCKS * 4 = 131,072 keypoints in one image.  Kept (same values) so the
+            // kernel stays correct if the launch shape or the capacity ever changes.
             cos_t = (float)vcr_cos((double)(ori * (float)(M_PI / 180)));
             sin_t = (float)vcr_sin((double)(ori * (float)(M_PI / 180)));
         }

@@ -51,6 +51,7 @@ def _declare(L):
     L.vo_o_recover_pose.argtypes = [P, P, P, I, P, P, P, P, P]
     L.vo_o_sift.argtypes = [P, I, I, P, P, I, P]
     L.vo_o_sift_n.argtypes = [P, I, I, I, P, P, I, P]
+    L.vo_o_sift_stages.argtypes = [P, I, I, P, P, P, C.c_int64, P, I, P]
     L.vo_o_retain_best.argtypes = [P, I, I, P]
     L.vo_o_retain_best_heap_selects.argtypes = []
     L.vo_o_bf_knn2.argtypes = [P, I, P, I, I, P, P]
@@ -264,6 +265,40 @@ def sift(img, cap=None, nfeatures=0):
         if n.value <= cap:
             return kp[:n.value].copy(), desc[:n.value].copy()
         cap = n.value
+
+
+def sift_stages(img):
+    """The stages of ``sift(img)``: a dict with ``up`` [2h, 2w] (the upsampled image before the
+    base blur), ``gauss`` / ``dog`` (per octave a float32 array [5, h_o, w_o]: layers 0..4),
+    ``extrema`` int32 [n, 4] (octave, layer, r, c) in scan order, and the counts ``n_extrema``,
+    ``n_refined`` (pass adjustLocalExtrema), ``n_raw`` (keypoints before removeDuplicatedSorted)
+    and ``n_final``."""
+    img = c_u8(img)
+    h, w = img.shape
+    info = np.zeros(8, np.int64)
+    rc = lib().vo_o_sift_stages(ptr(img), w, h, None, None, None, 0, None, 0, ptr(info))
+    if rc < 0:
+        raise RuntimeError(f"vo_o_sift_stages failed rc={rc}")
+    n_oct, n_ext, floats = int(info[0]), int(info[1]), int(info[5])
+    up = np.zeros((2 * h, 2 * w), np.float32)
+    gauss = np.zeros(max(floats, 1), np.float32)
+    dog = np.zeros(max(floats, 1), np.float32)
+    ext = np.zeros((max(n_ext, 1), 4), np.int32)
+    rc = lib().vo_o_sift_stages(ptr(img), w, h, ptr(up), ptr(gauss), ptr(dog), floats, ptr(ext), n_ext, ptr(info))
+    if rc != 0:
+        raise RuntimeError(f"vo_o_sift_stages failed rc={rc}")
+    gl, dl = [], []
+    off, ow, oh = 0, 2 * w, 2 * h
+    for o in range(n_oct):
+        if o > 0:
+            ow, oh = ow // 2, oh // 2
+        n = 5 * ow * oh
+        gl.append(gauss[off:off + n].reshape(5, oh, ow).copy())
+        dl.append(dog[off:off + n].reshape(5, oh, ow).copy())
+        off += n
+    assert off == floats
+    return {"up": up, "gauss": gl, "dog": dl, "extrema": ext[:n_ext].copy(), "n_extrema": n_ext,
+            "n_refined": int(info[2]), "n_raw": int(info[3]), "n_final": int(info[4])}
 
 
 def retain_best(response, n_points):

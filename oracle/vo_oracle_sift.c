@@ -615,19 +615,23 @@ int vo_o_sift(const uint8_t* image, int w, int h, float* kp_out, float* desc, in
     return vo_o_sift_n(image, w, h, 0, kp_out, desc, cap, n_out);
 }
 
-int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out, float* desc, int cap,
-                int* n_out)
+/* The scale space of one image: the 2x-upsampled input, nOct octaves of N_LAYERS + 3 Gaussian
+ * layers and N_LAYERS + 2 DoG layers. */
+typedef struct {
+    int nOct;
+    fimg_t up;
+    fimg_t* gp;
+    fimg_t* dog;
+} sift_ss_t;
+
+static void sift_scale_space(const uint8_t* image, int w, int h, double sigma, sift_ss_t* ss)
 {
-    if (!image || w < 1 || h < 1 || !n_out) return VO_O_EARG;
-    exptab_init();
-    const double sigma = 1.6;
     /* base: 2x upsample + blur to sigma */
     fimg_t up = fimg_new(2 * w, 2 * h);
     upsample2x(image, w, h, &up);
     float sig_diff = sqrtf(fmaxf((float)(sigma * sigma) - 0.5f * 0.5f * 4, 0.01f));
     fimg_t base = fimg_new(2 * w, 2 * h);
     gauss_blur(&up, &base, sig_diff);
-    free(up.d);
     int mn = base.w < base.h ? base.w : base.h;
     int nOct = (int)lrint(log((double)mn) / log(2.) - 2) + 1;
     double sig[N_LAYERS + 3];
@@ -662,6 +666,40 @@ int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out
             *d = fimg_new(a->w, a->h);
             for (size_t q = 0; q < (size_t)a->w * a->h; ++q) d->d[q] = b->d[q] - a->d[q];
         }
+    if (nOct <= 0) free(base.d);      /* no octave took ownership of the base image */
+    ss->nOct = nOct;
+    ss->up = up;
+    ss->gp = gp;
+    ss->dog = dog;
+}
+
+static void sift_scale_space_free(sift_ss_t* ss)
+{
+    free(ss->up.d);
+    for (int q = 0; q < ss->nOct * (N_LAYERS + 3); ++q) free(ss->gp[q].d);
+    for (int q = 0; q < ss->nOct * (N_LAYERS + 2); ++q) free(ss->dog[q].d);
+    free(ss->gp);
+    free(ss->dog);
+}
+
+/* What vo_o_sift_stages taps from the detection loop (NULL: nothing is recorded). */
+typedef struct {
+    int32_t* extrema;                 /* [ext_cap][4] (octave, layer, r, c) in scan order */
+    int ext_cap;
+    int n_extrema, n_refined, n_raw;
+} sift_tap_t;
+
+static int sift_impl(const uint8_t* image, int w, int h, int nfeatures, float* kp_out, float* desc, int cap,
+                     int* n_out, sift_ss_t* ss_out, sift_tap_t* tap)
+{
+    if (!image || w < 1 || h < 1 || !n_out) return VO_O_EARG;
+    exptab_init();
+    const double sigma = 1.6;
+    sift_ss_t ss;
+    sift_scale_space(image, w, h, sigma, &ss);
+    const int nOct = ss.nOct;
+    fimg_t* gp = ss.gp;
+    fimg_t* dog = ss.dog;
     /* extrema */
     const float threshold = (float)floor(0.5 * 0.04 / N_LAYERS * 255 * 1);
     size_t kcap = 1024, nk = 0;
@@ -684,9 +722,17 @@ int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out
                             }
                     }
                     if (!ext) continue;
+                    if (tap) {
+                        if (tap->extrema && tap->n_extrema < tap->ext_cap) {
+                            int32_t* e = tap->extrema + 4 * (size_t)tap->n_extrema;
+                            e[0] = o; e[1] = i; e[2] = r; e[3] = c;
+                        }
+                        ++tap->n_extrema;
+                    }
                     kp_t kpt;
                     int r1 = r, c1 = c, layer = i;
                     if (!adjust_local_extrema(dog, nOct, &kpt, o, &layer, &r1, &c1, (float)sigma)) continue;
+                    if (tap) ++tap->n_refined;
                     float scl_octv = kpt.size * 0.5f / (float)(1 << o);
                     float hist[SIFT_ORI_HIST_BINS];
                     float omax = calc_orientation_hist(&gp[o * (N_LAYERS + 3) + layer], c1, r1,
@@ -708,6 +754,7 @@ int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out
                     }
                 }
         }
+    if (tap) tap->n_raw = (int)nk;
     /* removeDuplicatedSorted */
     if (nk >= 2) {
         qsort(kps, nk, sizeof(kp_t), kp_cmp);
@@ -761,11 +808,47 @@ int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out
         }
     }
     free(kps);
-    for (int q = 0; q < nOct * (N_LAYERS + 3); ++q) free(gp[q].d);
-    for (int q = 0; q < nOct * (N_LAYERS + 2); ++q) free(dog[q].d);
-    free(gp);
-    free(dog);
+    if (ss_out) *ss_out = ss;         /* the caller frees it */
+    else sift_scale_space_free(&ss);
     return rc;
+}
+
+int vo_o_sift_n(const uint8_t* image, int w, int h, int nfeatures, float* kp_out, float* desc, int cap,
+                int* n_out)
+{
+    return sift_impl(image, w, h, nfeatures, kp_out, desc, cap, n_out, NULL, NULL);
+}
+
+int vo_o_sift_stages(const uint8_t* image, int w, int h, float* up, float* gauss, float* dog, int64_t gd_cap,
+                     int32_t* extrema, int ext_cap, int64_t* info)
+{
+    if (!info || ext_cap < 0 || gd_cap < 0) return VO_O_EARG;
+    sift_ss_t ss;
+    sift_tap_t tap = {extrema, ext_cap, 0, 0, 0};
+    int n_final = 0;
+    const int rc = sift_impl(image, w, h, 0, NULL, NULL, INT_MAX, &n_final, &ss, &tap);
+    if (rc != VO_O_OK) return rc;
+    if (up) memcpy(up, ss.up.d, sizeof(float) * (size_t)ss.up.w * ss.up.h);
+    int64_t off = 0;
+    for (int o = 0; o < ss.nOct; ++o)
+        for (int i = 0; i < N_LAYERS + 2; ++i) {
+            const fimg_t* g = &ss.gp[o * (N_LAYERS + 3) + i];
+            const fimg_t* d = &ss.dog[o * (N_LAYERS + 2) + i];
+            const int64_t n = (int64_t)g->w * g->h;
+            if (off + n <= gd_cap) {
+                if (gauss) memcpy(gauss + off, g->d, sizeof(float) * (size_t)n);
+                if (dog) memcpy(dog + off, d->d, sizeof(float) * (size_t)n);
+            }
+            off += n;
+        }
+    info[0] = ss.nOct;
+    info[1] = tap.n_extrema;
+    info[2] = tap.n_refined;
+    info[3] = tap.n_raw;
+    info[4] = n_final;
+    info[5] = off;
+    sift_scale_space_free(&ss);
+    return (off > gd_cap && (gauss || dog)) || (extrema && tap.n_extrema > ext_cap) ? VO_O_ECAP : VO_O_OK;
 }
 
 int vo_o_bf_knn2(const float* q, int nq, const float* t, int nt, int dim, int32_t* idx2, float* dist2)
