@@ -191,6 +191,17 @@ int vo_filter_pnp_triangulate(const vo_dims* d, const vo_opts* o, const vo_state
 /* cv2.goodFeaturesToTrack (:256) on pyramid level 0 of pyr[cur] -> state->corners. */
 int vo_gftt(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream);
 
+/* vo_corner_subpix on state->corners / nCorners after vo_gftt, reading level 0 of pyr[cur] (no
+ * reference counterpart: the reference adds goodFeaturesToTrack's integer positions, :256-268;
+ * engine option feature_subpix_win).  Same limits, VO_EARG with nothing launched outside them.  A
+ * chain whose status is not 0 or whose nCorners is <= 0 is left alone, so the capacity flag (-1)
+ * and the lists behind VO_ST_GFTT_NONE / VO_ST_GFTT_ONE reach vo_add_corners_finish unchanged.
+ * Asynchronous and capturable like the other stages; call between vo_gftt and
+ * vo_add_corners_finish on vo_gftt's stream. */
+int vo_gftt_subpix(const vo_dims* d, const vo_state* s, int cur,
+                   int32_t win_w, int32_t win_h, int32_t zero_w, int32_t zero_h,
+                   int32_t max_iters, double eps, vo_stream_t stream);
+
 /* Diagnostics: the cornerMinEigenVal / cornerHarris map goodFeaturesToTrack thresholds
  * (featureselect.cpp), written to state->eig ([B][W*H] f32) with its max in eig_max.
  * vo_gftt itself never stores this map. */
@@ -278,6 +289,26 @@ int vo_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s,
 int vo_filter_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s,
                                  int32_t refine_iters, double refine_ftol, double* refine_info,
                                  vo_stream_t stream);
+
+/* Sub-pixel refinement of corner positions in the form of cv2.cornerSubPix; the project's own
+ * definition (the NumPy restatement tests/test_subpix_ref.py), reproduced bit for bit.
+ * Plain device images: image b is H rows of W u8 pixels at img + b * img_stride, `pitch` bytes
+ * between rows (pitch >= W).  pts [B][cap][2] with counts[B]: pts[b][0..counts[b]) are refined in
+ * place, rows past the count are not touched, a count <= 0 is skipped.  (win_w, win_h): half sizes
+ * of the window, 1..7 each (the window is (2 win_w + 1) x (2 win_h + 1)); (zero_w, zero_h): half
+ * sizes of the central zone with weight 0, (-1, -1) = none, else 0 <= zero_w < win_w and
+ * 0 <= zero_h < win_h; max_iters 1..100; eps finite and >= 0 (a step of at most eps pixels ends
+ * the walk).  A point that would end more than the half-window from its start on an axis, or
+ * outside the image, keeps its start value; a start outside [0,W) x [0,H) is left alone.  iters
+ * [B][cap] (NULL = not wanted): iterations walked per point.  Anything outside these limits, or a
+ * count above cap, returns VO_EARG with nothing written.  The counts are device memory, so the
+ * capacity check reads them back first: unlike the other entry points this one waits for the
+ * stream before it launches and cannot be captured into a graph (vo_gftt_subpix can). */
+int vo_corner_subpix(int B, const uint8_t* img, int64_t img_stride, int32_t pitch, int W, int H,
+                     float* pts, const int32_t* counts, int32_t cap,
+                     int32_t win_w, int32_t win_h, int32_t zero_w, int32_t zero_h,
+                     int32_t max_iters, double eps, int32_t* iters /* [B][cap] or NULL */,
+                     vo_stream_t stream);
 
 /* cv2.triangulatePoints (:188) for float32 points: P1,P2 [n][12] (row-major 3x4 each,
  * one pair per point), x1,x2 [n][2] -> out [n][4] float32. */

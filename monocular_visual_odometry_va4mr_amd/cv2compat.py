@@ -9,6 +9,9 @@ Same names, argument meanings, dtypes and output shapes as the OpenCV 4.6 calls 
     BFMatcher.knnMatch    :36,:229    findEssentialMat      :308
     recoverPose           :315
 
+and, beyond the reference, cornerSubPix (the call behind goodFeaturesToTrack in most KLT front
+ends) and solvePnPRefineLM, in this project's own arithmetic.
+
 Each call copies numpy inputs to the device, runs the HIP kernels and copies results
 back (the drop-in mode; the device-resident path is engine.Engine).  Installing this
 module as ``sys.modules['cv2']`` lets the reference class itself run on the GPU.
@@ -161,6 +164,55 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), m
                                     flags, _p(out), _p(st), _p(err), _stream()), "vo_lk_points_ex")
     return (out.cpu().numpy().reshape(shape), st.cpu().numpy().reshape(-1, 1),
             err.cpu().numpy().reshape(-1, 1))
+
+
+# ---------------------------------------------------------------- cornerSubPix
+SUBPIX_MAX_HALF_WIN = 7
+
+
+def cornerSubPix(image, corners, winSize, zeroZone, criteria):
+    """cv2.cornerSubPix's form over vo_corner_subpix: ``corners`` (float32, (N, 1, 2) or (N, 2)) are
+    refined in place on the uint8 grayscale ``image`` and returned in the same shape.  ``winSize``
+    is the half-window (w, h), 1..7 each (larger raises NotImplementedError); ``zeroZone``
+    (-1, -1) or half sizes inside the window.  The iteration is this project's own, not
+    OpenCV's arithmetic: criteria's count is the iteration limit, clamped to 1..100 (100 without
+    the COUNT bit), its epsilon the step length that ends the walk (max(eps, 0); 0 without the
+    EPS bit).  The image is not written."""
+    img = _gray(image)
+    if not isinstance(corners, np.ndarray) or corners.dtype != np.float32:
+        raise error("cornerSubPix: corners must be a float32 array (checkVector(2, CV_32F))")
+    if not ((corners.ndim == 2 and corners.shape[1] == 2) or (corners.ndim == 3 and corners.shape[1:] == (1, 2))):
+        raise error("cornerSubPix: corners must have shape (N, 2) or (N, 1, 2)")
+    try:
+        w, h = (int(v) for v in winSize)
+        zw, zh = (int(v) for v in zeroZone)
+        ctype, count, eps = criteria
+        ctype, count, eps = int(ctype), int(count), float(eps)
+    except (TypeError, ValueError) as e:
+        raise error(f"cornerSubPix: bad winSize, zeroZone or criteria ({e})") from None
+    if w < 1 or h < 1:
+        raise error("cornerSubPix: winSize must be at least (1, 1)")
+    if w > SUBPIX_MAX_HALF_WIN or h > SUBPIX_MAX_HALF_WIN:
+        raise NotImplementedError(f"cornerSubPix: half-windows above {SUBPIX_MAX_HALF_WIN} are not supported "
+                                  f"(got {(w, h)})")
+    if (zw, zh) != (-1, -1) and not (0 <= zw < w and 0 <= zh < h):
+        raise error("cornerSubPix: zeroZone must be (-1, -1) or lie inside the window")
+    max_iters = min(max(count, 1), 100) if ctype & TERM_CRITERIA_COUNT else 100
+    eps = max(eps, 0.0) if ctype & TERM_CRITERIA_EPS else 0.0
+    if not math.isfinite(eps):
+        raise error("cornerSubPix: the criteria's epsilon must be finite")
+    n = corners.shape[0]
+    if n == 0:
+        return corners
+    H, W = img.shape
+    dev = _dev()
+    d_img = torch.from_numpy(img).to(dev)
+    d_pts = torch.from_numpy(np.ascontiguousarray(corners.reshape(n, 2))).to(dev)
+    cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+    L.check(L.lib().vo_corner_subpix(1, _p(d_img), W * H, W, W, H, _p(d_pts), _p(cnt), n, w, h, zw, zh, max_iters,
+                                     C.c_double(eps), None, _stream()), "vo_corner_subpix")
+    corners[...] = d_pts.cpu().numpy().reshape(corners.shape)
+    return corners
 
 
 # ---------------------------------------------------------------- PnP (:343)

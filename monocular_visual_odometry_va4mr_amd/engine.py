@@ -12,7 +12,8 @@ The reference's per-frame control flow maps to stages as
     feature_tracking :271-290   -> vo_pyr_build(cur) (pyramid + derivatives) + vo_track(prev)
     PnP step        :338-358    -> vo_pnp
     triangulation   :366-367    -> vo_triangulate
-    feature_adding  :369        -> vo_gftt(cur) + vo_add_corners_finish (also :371-373)
+    feature_adding  :369        -> vo_gftt(cur) [+ vo_gftt_subpix(cur) with the option
+                                   feature_subpix_win] + vo_add_corners_finish (also :371-373)
 
 (by default the filtering of feature_tracking, PnP and triangulation run as one launch:
 vo_track_lk + vo_filter_pnp_triangulate; VO_PNP_TRI_SPLIT=1 selects the separate calls)
@@ -122,6 +123,49 @@ def parse_refine(options: dict) -> tuple[int, float]:
     return int(it), float(ftol)
 
 
+SUBPIX_MAX_HALF_WIN = 7
+
+
+def parse_subpix(options: dict):
+    """None (off), or (win_w, win_h, zero_w, zero_h, max_iters, eps) of an options dict, validated:
+    feature_subpix_win an integer or a (w, h) pair of half-windows 1..7 (absent / None = off),
+    feature_subpix_iters an integer in 1..100 (default 20), feature_subpix_eps finite and >= 0
+    (default 0.03), feature_subpix_zero_zone (-1, -1) (the default: none) or half sizes inside the
+    window.  The companion keys are validated whether the refinement is on or not."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    def pair(v, what):
+        if is_int(v):
+            return int(v), int(v)
+        if isinstance(v, (tuple, list, np.ndarray)) and len(v) == 2 and all(is_int(x) for x in v):
+            return int(v[0]), int(v[1])
+        raise ValueError(f"{what} must be an integer or a pair of integers")
+
+    it = options.get("feature_subpix_iters")
+    it = 20 if it is None else it
+    if not is_int(it) or not 1 <= int(it) <= 100:
+        raise ValueError("feature_subpix_iters must be an integer in 1..100")
+    eps = options.get("feature_subpix_eps")
+    eps = 0.03 if eps is None else eps
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or \
+            not (math.isfinite(eps) and eps >= 0):
+        raise ValueError("feature_subpix_eps must be a finite number >= 0")
+    zz = options.get("feature_subpix_zero_zone")
+    zw, zh = (-1, -1) if zz is None else pair(zz, "feature_subpix_zero_zone")
+    win = options.get("feature_subpix_win")
+    if win is None:
+        if (zw, zh) != (-1, -1) and (zw < 0 or zh < 0):
+            raise ValueError("feature_subpix_zero_zone must be (-1, -1) or half sizes >= 0")
+        return None
+    w, h = pair(win, "feature_subpix_win")
+    if not (1 <= w <= SUBPIX_MAX_HALF_WIN and 1 <= h <= SUBPIX_MAX_HALF_WIN):
+        raise ValueError(f"feature_subpix_win: half-windows must be in 1..{SUBPIX_MAX_HALF_WIN}")
+    if (zw, zh) != (-1, -1) and not (0 <= zw < w and 0 <= zh < h):
+        raise ValueError("feature_subpix_zero_zone must be (-1, -1) or lie inside the window")
+    return w, h, zw, zh, int(it), float(eps)
+
+
 class Engine:
     """B chains of the VO per-frame step on one device."""
 
@@ -216,6 +260,10 @@ class Engine:
         # pnp_refine_ftol: its relative cost tolerance
         self.pnp_refine_iters, self.pnp_refine_ftol = parse_refine(options)
         self._refine_info = z(B, 4, dt=torch.float64) if self.pnp_refine_iters else None
+        # feature_subpix_win (this build's own key, absent / None = off): the corners of vo_gftt are
+        # refined to sub-pixel positions by vo_gftt_subpix before feature adding reads them (DESIGN
+        # 5e); feature_subpix_iters, feature_subpix_eps, feature_subpix_zero_zone.  No buffer of its own.
+        self.feature_subpix = parse_subpix(options)
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -384,8 +432,17 @@ class Engine:
             run(0, main, lambda: lib.vo_pyr_build(pd, ps, cur, fp, self.W * self.H, sm))
         if forked:
             side.wait_stream(main)                                # pyramid(cur) ready, last step's corners consumed
+        gftt = lambda: lib.vo_gftt(pd, po, ps, cur, ss)
+        if self.feature_subpix is not None:
+            # the refinement directly behind vo_gftt, on its stream and inside its stage
+            sw, sh, szw, szh, sit, seps = self.feature_subpix
+            seps = C.c_double(seps)
+
+            def gftt():
+                rc = lib.vo_gftt(pd, po, ps, cur, ss)
+                return rc if rc != 0 else lib.vo_gftt_subpix(pd, ps, cur, sw, sh, szw, szh, sit, seps, ss)
         if not gftt_late:
-            run(4, side, lambda: lib.vo_gftt(pd, po, ps, cur, ss))
+            run(4, side, gftt)
         fused = getattr(self, "fuse_pnp_tri", os.environ.get("VO_PNP_TRI_SPLIT") != "1")
         # fused: tracking leaves the status filtering (:283-290) to the PnP launch, which runs it
         # first in each chain's block (one kernel boundary fewer on the step's critical path)
@@ -408,7 +465,7 @@ class Engine:
         else:
             run(1, main, lambda: track(pd, po, ps, prev, sm))
         if gftt_late:
-            run(4, side, lambda: lib.vo_gftt(pd, po, ps, cur, ss))
+            run(4, side, gftt)
         ev_corners = None
         if forked:
             ev_corners = torch.cuda.Event()
