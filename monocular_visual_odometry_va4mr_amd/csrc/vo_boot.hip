@@ -852,8 +852,6 @@ __global__ void k_copy_pose(vo_dims d, vo_state s, const double* R, const double
 }  // namespace
 
 // ======================================================================= host side
-#define VO_STREAM(s) ((hipStream_t)(s))
-static inline int hip_rc() { return hipGetLastError() == hipSuccess ? VO_OK : VO_EHIP; }
 
 static void fill_ess(EssArgs& A, const vo_opts* o, const float* p0, const float* p1, const int32_t* counts, int cap,
                      double prob, double thr, int iters, double* E, uint8_t* mask, int32_t* ok, double* work,

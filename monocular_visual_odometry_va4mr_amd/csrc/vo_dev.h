@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/vo_hip.h"
 
@@ -16,6 +17,15 @@ VO_DEV int refl101(int p, int len)
     if (len == 1) return 0;
     while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - p - 2;
     return p;
+}
+
+// LDS written by some lanes of a wave is visible to its other lanes afterwards (single-wave
+// kernels, where no block barrier is needed)
+VO_DEV void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 VO_DEV int64_t wave_sum_i64(int64_t v)
@@ -202,6 +212,19 @@ VO_DEV uint32_t rng_next(uint64_t& s)
 }
 
 #define DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
+
+// host: a stream handle of the C ABI, and the launch status the entry points return
+#define VO_STREAM(s) ((hipStream_t)(s))
+static inline bool hip_ok() { return hipGetLastError() == hipSuccess; }
+static inline int hip_rc() { return hip_ok() ? VO_OK : VO_EHIP; }
+
+// host: an integer tuning knob from the environment (tools/README.md lists them); the call sites
+// keep the value in a static const, so it is read once per process
+static inline int vo_env_int(const char* name, int dflt)
+{
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // host: compute units of the current device, cached per device id (launch-shape decisions of
 // the C ABI entry points; a benign race only stores the same value twice), or the count set by

@@ -95,13 +95,6 @@ VO_DEV void svd_jacobi(double* A, double* w, double* V)
     }
 }
 
-VO_DEV void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // svd_jacobi<M, N> executed by one whole wave with A [M*N], w [N], V [N*N] in LDS
 // (row-major), M, N <= 64.  Same cyclic pair order and the same floating-point
 // operations: every lane forms the three column sums in the scalar order from

@@ -629,7 +629,6 @@ __global__ void __launch_bounds__(256) k_bf_fixup(BfArgs A, const float* __restr
 }  // namespace
 
 // ======================================================================= host side
-#define VO_STREAM(s) ((hipStream_t)(s))
 
 static int bf_tsplit(int B, int qcap, int tcap, int qb, int tt)
 {

@@ -872,12 +872,6 @@ VO_DEV void pnp_apply_split(const vo_dims& d, const vo_state& s, double* rvec, c
 
 __global__ void __launch_bounds__(256) k_pnp_ransac(PnPArgs A) { pnp_ransac_block(A); }
 
-__global__ void __launch_bounds__(256) k_pnp_apply(vo_dims d, vo_state s, const double* rvec, const double* tvec,
-                                                   const int32_t* success, const uint8_t* mask_all)
-{
-    pnp_apply_block(d, s, rvec, tvec, success, mask_all);
-}
-
 // the engine's PnP stage as one launch: RANSAC + EPnP, then (after a block barrier, which
 // makes thread 0's rvec / tvec / success visible to the block) the epilogue -- a second,
 // separate launch had to wait for CUs behind the other stream group's LK blocks
@@ -1809,8 +1803,6 @@ __global__ void k_rodrigues(int n, int to_matrix, const double* in, double* out)
 }  // namespace
 
 // ======================================================================= host side
-#define VO_STREAM(s) ((hipStream_t)(s))
-static inline int hip_rc() { return hipGetLastError() == hipSuccess ? VO_OK : VO_EHIP; }
 
 static void fill_pnp(PnPArgs& P, const vo_opts* o)
 {
@@ -1861,11 +1853,7 @@ extern "C" int vo_pnp_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, 
     PnPArgs P;
     fill_pnp_engine(P, d, o, s);
     hipStream_t st = VO_STREAM(stream);
-    static const int split = [] { const char* e = getenv("VO_PNP_SPLIT"); return e ? atoi(e) : 0; }();
-    if (split == 1) {                     // the two-launch form (A/B measurements)
-        hipLaunchKernelGGL(k_pnp_ransac, dim3(d->B), dim3(256), 0, st, P);
-        hipLaunchKernelGGL(k_pnp_apply, dim3(d->B), dim3(256), 0, st, *d, *s, P.rvec, P.tvec, P.success, P.mask);
-    } else if (d->B > (device_cus() > 0 ? device_cus() : 256)) {
+    if (d->B > (device_cus() > 0 ? device_cus() : 256)) {
         // more chains than CUs: two blocks per CU (as vo_pnp_triangulate)
         hipLaunchKernelGGL(k_pnp_fused<VO_PNP_WPE>, dim3(d->B), dim3(256), 0, st, P, *d, *s);
     } else {
@@ -1944,7 +1932,7 @@ static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s,
     // more chains than CUs: the 2-waves/SIMD build (two blocks per CU, some registers spilled);
     // otherwise every block has a CU of its own and the unconstrained build is faster
     // (VO_PNP_TRI_WPE=1|2 forces one build: measurement option)
-    static const int force = [] { const char* e = getenv("VO_PNP_TRI_WPE"); return e ? atoi(e) : 0; }();
+    static const int force = vo_env_int("VO_PNP_TRI_WPE", 0);
     const int n_cu = device_cus() > 0 ? device_cus() : 256;      // of the current device
     const bool two = force ? force == 2 : d->B > n_cu;
     if (refine_iters > 0) {
@@ -1989,7 +1977,7 @@ extern "C" int vo_add_corners_finish(const vo_dims* d, const vo_opts* o, const v
     A.min_dist = o->feature_min_dist;
     A.boot = 0;
     // the lean form from 256 chains per launch (VO_ADD_LEAN=0 / 1 forces it off / on)
-    static const int lean_env = [] { const char* e = getenv("VO_ADD_LEAN"); return e ? atoi(e) : -1; }();
+    static const int lean_env = vo_env_int("VO_ADD_LEAN", -1);
     if (lean_env >= 0 ? lean_env == 1 : d->B >= 256)
         hipLaunchKernelGGL(k_add_finish_lean, dim3(d->B), dim3(ADD_LEAN_THREADS), 0, VO_STREAM(stream), A);
     else

@@ -1406,8 +1406,6 @@ __global__ void __launch_bounds__(256) k_ratio(const float* kp0, const float* kp
 }  // namespace
 
 // ======================================================================= host side
-#define VO_STREAM(s) ((hipStream_t)(s))
-static inline int hip_rc() { return hipGetLastError() == hipSuccess ? VO_OK : VO_EHIP; }
 
 extern "C" int vo_sift_plan(vo_sift_buf* sb, int W, int H)
 {
@@ -1510,7 +1508,7 @@ extern "C" int vo_sift_batch(const vo_sift_buf* sb, int B, const uint8_t* imgs, 
         const float* kern = sb->consts + layer * KTAPS;
         // packed compile-time-size form for the SIFT kernel sizes (VO_SIFT_BLUR_GENERIC=1: the
         // runtime-size kernel; both identical)
-        static const bool generic = [] { const char* e = getenv("VO_SIFT_BLUR_GENERIC"); return e && atoi(e) == 1; }();
+        static const bool generic = vo_env_int("VO_SIFT_BLUR_GENERIC", 0) == 1;
         switch (generic ? 0 : ks[layer]) {
         case 11: hipLaunchKernelGGL(k_blur_tile_n<11>, g, dim3(256), 0, st, src, src_stride, dst, gs, dog, ds, w, h, kern); return;
         case 13: hipLaunchKernelGGL(k_blur_tile_n<13>, g, dim3(256), 0, st, src, src_stride, dst, gs, dog, ds, w, h, kern); return;

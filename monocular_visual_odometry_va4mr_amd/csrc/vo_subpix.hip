@@ -15,8 +15,6 @@
 #include "vo_crmath.h"
 #include "vo_dev.h"
 
-#define VO_STREAM(s) ((hipStream_t)(s))
-
 #define SPX_MAXW 7
 #define SPX_PATCH ((2 * SPX_MAXW + 3) * (2 * SPX_MAXW + 3))      // 289 floats
 #define SPX_DET_MIN 0x1p-104                                      // DBL_EPSILON^2

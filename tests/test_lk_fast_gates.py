@@ -1,5 +1,5 @@
 """The f32 fast paths k_lk_w uses for two of OpenCV's decisions (round 6) never decide differently
-from the exact computation (csrc/vo_image.hip, k_lk_w; lkpyramid.cpp semantics):
+from the exact computation (csrc/vo_lk.hip, k_lk_w; lkpyramid.cpp semantics):
 
 * the minEig gate  (A22 + A11 - sqrtf(t)) / (2 WW WH) < min_eig  (correctly rounded f32 sqrt and
   division) is first decided from the raw v_sqrt_f32 (modelled here as the correctly rounded sqrt

@@ -7,7 +7,7 @@
 //           guarantees 10 complete) -- the shape of the dropped k_lk_w variant (24 reads,
 //           lgkmcnt(14));
 //   mode 1: 15 ds_write_b8 + 2 ds_read_b32, s_waitcnt lgkmcnt(1), copy the first read -- the
-//           shape lgkm_check reports in k_pyr_level<true,32> / k_pyr01 (17 ops, lgkmcnt(1)).
+//           shape lgkm_check reports in pyr_tile<true,32> (k_pyr01) (17 ops, lgkmcnt(1)).
 // conflict = 1 puts every lane of an instruction on one LDS bank (64-way serialisation: long
 // latency, so an early release would show).  Prints the number of wrong copies per case.
 #include <hip/hip_runtime.h>
