@@ -207,6 +207,12 @@ int vo_gftt_subpix(const vo_dims* d, const vo_state* s, int cur,
  * vo_gftt itself never stores this map. */
 int vo_gftt_eigmap(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream);
 
+/* Diagnostics: the eigen pass of vo_gftt alone.  gf_keys [B][ccap] receives every local maximum
+ * with v > 0 among the interior pixels as (fkey(v) << 32 | y * W + x), in no particular order,
+ * gf_n their count per chain and eig_max the map's maximum (fkey form); no quality gate and no
+ * selection runs, so the key set can be read before vo_gftt's selection consumes it. */
+int vo_gftt_keys(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream);
+
 /* feature_adding distance filter + append (:258-268) and the pose/num_pts append
  * (:371-373).  Call after vo_gftt. */
 int vo_add_corners_finish(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream);

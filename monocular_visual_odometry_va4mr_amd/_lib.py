@@ -146,6 +146,7 @@ def _declare(L):
         "vo_filter_pnp_triangulate": ([D, O, S, P], C.c_int),
         "vo_gftt": ([D, O, S, C.c_int, P], C.c_int),
         "vo_gftt_eigmap": ([D, O, S, C.c_int, P], C.c_int),
+        "vo_gftt_keys": ([D, O, S, C.c_int, P], C.c_int),
         "vo_gftt_subpix": ([D, S, C.c_int, i32, i32, i32, i32, i32, f64, P], C.c_int),
         "vo_corner_subpix": ([C.c_int, P, i64, i32, C.c_int, C.c_int, P, P, i32, i32, i32, i32, i32, i32, f64, P, P],
                              C.c_int),

@@ -8,6 +8,7 @@
 #include "vo_dev.h"
 
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -163,17 +164,39 @@ __global__ void __launch_bounds__(256) k_eignms(EigParams P)
 // as a row-streaming kernel.  One wave owns an E3_OUT-column x E3_TH-row tile; lane = image
 // column (3 halo lanes each side) and the wave slides down the rows keeping every
 // intermediate in registers: the Sobel row terms of the last two image rows, the box row
-// sums of the last two gradient rows, the last two eigen rows.  Horizontal neighbours come
-// from the adjacent lanes through DPP wave shifts.  Integers, the double expression of
-// lambda_min, the reflect-101 handling and the emitted key set are those of k_eignms (the
-// parity tests compare corner lists and eigen maps bit for bit).  Keys are gathered in an
-// LDS buffer and appended with one atomic per E3_CAP-sized batch.
+// sums of the last two gradient rows, the NMS state of the last two eigen rows.  Horizontal
+// neighbours come from the adjacent lanes through DPP wave shifts.  Integers, the double
+// expression of lambda_min, the reflect-101 handling and the emitted key set are those of
+// k_eignms (the parity tests compare corner lists and eigen maps bit for bit).
+//
+// The exact value v = (float)(((double)T - sqrt((double)D)) * sc) is only consumed where a key is
+// emitted (local maxima with v > 0) and in the per-chain maximum; everywhere else it is compared
+// with its eight neighbours.  k_eig3<false> therefore runs the row loop on an f32 interval
+// [lo, hi] that provably contains v (e3_interval), queues the pixels the intervals cannot rule
+// out as maxima, and evaluates the double expression for queued pixels only, 64 at a time.
+// k_eig3<true> evaluates it for every pixel (the eigen map of vo_gftt_eigmap, VO_EIG_EXACT=1).
 #define E3_OUT 58
 #define E3_TH 64
-#define E3_CAP 512
+#define E3_CAP 512            // key buffer of the exact-everywhere form
+#define E3_QCAP 256           // queue of possible maxima (16 bytes each), emptied after every 8 rows
+#define E3_Q_MAXONLY 0x10000  // entry counts in the maximum only (image border: no NMS there)
+#define E3_Q_DECIDED 0x20000  // entry's lower bound is >= every neighbour's upper bound
 
-VO_DEV int dpp_from_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, false); }   // lane i <- i-1
-VO_DEV int dpp_from_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, false); }  // lane i <- i+1
+// lane i <- i-1 / i+1; the lane without a neighbour reads 0 (bound_ctrl)
+VO_DEV int dpp_from_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
+VO_DEV int dpp_from_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
+VO_DEV float dpp_max_lr(float v)
+{
+    const int i = __float_as_int(v);
+    return fmaxf(__int_as_float(dpp_from_left(i)), __int_as_float(dpp_from_right(i)));
+}
+VO_DEV int dpp_max_lr(int v) { return max(dpp_from_left(v), dpp_from_right(v)); }
+
+// lanes below this one set in a ballot mask
+VO_DEV int lane_prefix(uint64_t m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
 
 // sqrt of a double holding an integer in [0, 2^53): the compiler's correctly rounded sequence
 // (v_rsq_f64 + Newton steps with a final fma correction) without its range reduction for inputs
@@ -193,9 +216,73 @@ VO_DEV double sqrt_int_f64(double x)
     return x == 0.0 ? 0.0 : g;
 }
 
-__global__ void __launch_bounds__(64) k_eig3(EigParams P)
+// lambda_min * sc from the box sums: T = sxx + syy, dd = sxx - syy (the products are exact in
+// double: |dd|, |sxy| < 2^24).  D <= T^2 (Cauchy-Schwarz on the box sums) and the square root is
+// correctly rounded, so sqrt(D) <= T and v >= +0 at every pixel.
+VO_DEV float e3_exact(int T, int dd, int sxy, double sc)
 {
-    __shared__ uint64_t kbuf[E3_CAP];
+    const double Dd = (double)dd * (double)dd + 4.0 * ((double)sxy * (double)sxy);
+    return (float)(((double)T - sqrt_int_f64(Dd)) * sc);
+}
+
+// f32 interval around e3_exact's value v.  With u = 2^-24, s = sqrt(D), A = (T + s) * sc:
+//   Tf = fl(T)                      = T (1 + t),  |t| <= u      (T < 2^25; dd, sxy are exact)
+//   Df = fl(fl(dd^2) + 4 fl(sxy^2)) = D (1 + d),  |d| <= 2u + u^2  (non-negative terms)
+//   sf = v_sqrt_f32(Df), taken as 2 ulp off     = s (1 + e),  |e| <= u + 4u + O(u^2) <= 5.01u
+//   vt = fl(fl(Tf - sf) * fl(sc))   = ((T - s) + T t - s e)(1 + h) sc,  |h| <= 3.01u
+// so |vt - (T - s) sc| <= u (T + 5.01 s + 3.01 (T - s)) (1 + 4u) sc <= 4.02 u A.  The double
+// sequence and its final rounding to float put v within 1.01 u A of (T - s) sc, and rounding
+// lo = fl(vt - eps), hi = fl(vt + eps) moves a bound by at most u (|vt| + eps) <= 1.01 u A:
+// 6.04 u A in all.  eps = fl(fl(2^-21 sc) * fl(Tf + sf)) >= 8 u A (1 - 9u) > 7.99 u A covers it
+// with a third to spare.  Nothing here under- or overflows: sums are integers below 2^25,
+// D < 2^49, and a non-zero Tf - sf is at least 2^-24, so vt >= 2^-49 in magnitude or 0.
+// All sums zero gives vt = eps = 0 and v = 0 exactly.
+// v >= 0 (e3_exact), so the lower bound is clamped at 0 and hi >= v >= 0: both bounds are
+// non-negative floats, which order as their bit patterns do, and the NMS compares and maximises
+// them as integers (DPP and v_max3_i32 directly, no NaN canonicalisation).  A -0 would only make
+// a bound look lower than it is, which flags more, never less.
+VO_DEV void e3_interval(int T, int dd, int sxy, float scf, float epk, int& lo, int& hi)
+{
+    const float Tf = (float)T, df = (float)dd, xf = (float)sxy;
+    const float sf = __builtin_amdgcn_sqrtf(df * df + 4.f * (xf * xf));
+    const float vt = (Tf - sf) * scf;
+    const float eps = epk * (Tf + sf);
+    lo = __float_as_int(fmaxf(vt - eps, 0.f));
+    hi = __float_as_int(vt + eps);
+}
+
+// one pixel's box sums from the image, with k_eignms's arithmetic and reflect-101 handling (slow:
+// only for the neighbours of a queued pixel whose interval overlaps theirs, and for rows the
+// queue had no room for).  img is pixel (0,0) of a level-0 image (below 2^31 bytes), 0 <= x < W,
+// 0 <= y < H.
+VO_DEV void e3_sums(const uint8_t* img, int pitch, int W, int H, int x, int y, int& T, int& dd, int& sxy)
+{
+    const uint8_t* org = img - pitch - 1;                // pixel (-1,-1): offsets below are >= 0
+    int sxx = 0, syy = 0;
+    sxy = 0;
+#pragma unroll 1
+    for (int q = 0; q < 9; ++q) {
+        const int i = q / 3, j = q - 3 * i;
+        const int cx = refl101(x - 1 + j, W), cy = refl101(y - 1 + i, H);
+        const uint8_t* u = org + (uint32_t)(cy * pitch + cx);     // row above, left neighbour first
+        const uint8_t* c = u + pitch;
+        const uint8_t* l = c + pitch;
+        const int gx = (u[2] - u[0]) + 2 * (c[2] - c[0]) + (l[2] - l[0]);
+        const int gy = (l[0] - u[0]) + 2 * (l[1] - u[1]) + (l[2] - u[2]);
+        sxx += gx * gx;
+        sxy += gx * gy;
+        syy += gy * gy;
+    }
+    T = sxx + syy;
+    dd = sxx - syy;
+}
+
+// 8 waves per SIMD (64 VGPRs): the kernel hides its latencies with occupancy, and rides beside LK
+template <bool EXACT>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_eig3(EigParams P)
+{
+    __shared__ uint64_t kbuf[EXACT ? E3_CAP : 1];
+    __shared__ int4 qbuf[EXACT ? 1 : E3_QCAP];
     const int tiles = P.tiles_x * P.tiles_y;
     const int item = xcd_item(blockIdx.x, P.B * tiles);
     if (item >= P.B * tiles) return;
@@ -206,20 +293,30 @@ __global__ void __launch_bounds__(64) k_eig3(EigParams P)
     const int W = P.W, H = P.H;
     const int lane = lane_id();
     const int c = x0 - 3 + lane;                         // image column of this lane
-    const int cl = min(c, W + 2);                        // loads stay inside the padded row
-    const uint8_t* colp = P.pyr + (int64_t)b * P.pstride + P.off + (int64_t)VO_BORDER * P.pitch + VO_BORDER + cl;
+    const uint8_t* img = P.pyr + (int64_t)b * P.pstride + P.off + (int64_t)VO_BORDER * P.pitch + VO_BORDER;
+    // row loads: one wave-uniform pointer (row -1, column x0-3: inside the border) plus a 32-bit
+    // offset per lane (a level-0 image is below 2^31 bytes); cl is the lane, held inside the
+    // padded row (column W+2 at most), so cl == lane for every own lane
+    const uint8_t* colp = img - P.pitch + (x0 - 3);
+    const uint32_t cl = (uint32_t)min(lane, W + 2 - (x0 - 3));
+    auto load_row = [&](int row) { return (int)colp[(uint32_t)((row + 1) * P.pitch) + cl]; };
     const int g0 = max(y0 - 2, 0), g1 = min(y0 + E3_TH + 1, H - 1);   // gradient / box rows
     const int e0 = max(y0 - 1, 0);                                     // first eigen row
     const int o0 = max(y0, 1), o1 = min(y0 + E3_TH, H - 1);            // NMS rows [o0, o1)
     const int m1 = min(y0 + E3_TH, H);                                 // own rows [y0, m1)
     const bool own = lane >= 3 && lane < 3 + E3_OUT && c < W;
-    const bool nms_col = own && c >= 1 && c < W - 1;
+    const bool edge_col = own && (c == 0 || c == W - 1);               // in the maximum, not in the NMS
+    const bool nms_col = own && !edge_col;
     const bool hedge = x0 == 0 || x0 + E3_OUT + 3 > W - 1;             // tile reaches column 0 or W-1
     const double s = 1.0 / ((double)(1 << 2) * 3 * 255.0);
     const double sc = s * s * 0.5;
-    uint32_t kmax = 0;
-    int nbuf = 0;
+    const float scf = (float)sc, epk = (float)(sc * (1.0 / 2097152.0));
+    // every own pixel has v >= +0 (e3_exact), so the interval form starts the maximum there and
+    // only adds the pixels it evaluates exactly
+    uint32_t kmax = (!EXACT && own) ? fkey(0.f) : 0u;
     uint64_t* out = P.keys ? P.keys + (int64_t)b * P.ccap : nullptr;
+    // ---- exact-everywhere form: keys gathered in kbuf, one atomic per E3_CAP-sized batch
+    int nbuf = 0;
     auto flush = [&]() {
         int base = 0;
         if (lane == 0) base = atomicAdd(&P.nkeys[b], nbuf);
@@ -230,63 +327,152 @@ __global__ void __launch_bounds__(64) k_eig3(EigParams P)
         wave_lds_sync();
         nbuf = 0;
     };
-    int hsA = 0, hdA = 0, hsB = 0, hdB = 0;              // Sobel row terms of image rows ir-2, ir-1
-    int xA = 0, yA = 0, zA = 0, xB = 0, yB = 0, zB = 0;  // box row sums (xx, xy, yy) of rows pr-2, pr-1
-    float eA = 0.f, eB = 0.f;                            // eigen rows r-2, r-1
-    // the NMS maxima of those rows, each formed once when its row is new: 3-neighbour max of
-    // row r-2, left / right max of row r-1 (fmaxf is exact and order-free on these values)
+    float eB = 0.f;                                      // eigen row r-1
+    // the NMS maxima of the last two rows, each formed once when its row is new: 3-neighbour max
+    // of row r-2, left / right max of row r-1 (fmaxf is exact and order-free on these values)
     float mA3 = 0.f, mB2 = 0.f;
-    // eigen row r from the box row sums of rows r-1, r, r+1; then the NMS of row r-1
-    auto eig_row = [&](int r, int ax, int ay, int az, int bx, int by, int bz, int cx, int cy, int cz) {
+    // ---- interval form: the same row state over the lower (nA3, nB2) and upper (nA3H, nB2H)
+    // bounds, the bounds and box sums of row r-1, and the queue of possible maxima
+    int loB = 0, hiB = 0, nA3 = 0, nB2 = 0, nA3H = 0, nB2H = 0;
+    int TB = 0, dB = 0, sB = 0;
+    int nq = 0;
+    uint64_t ovf = 0;                                    // own rows (bit rn - y0) the queue had no room for
+    // one batch of up to 64 pixels, one per lane, from their box sums: the exact value, the
+    // maximum, the eight neighbours' exact values (from the image) where the intervals left the
+    // NMS open, and the keys appended with one atomic
+    auto batch = [&](int4 e, bool act) {
+        const float v = e3_exact(e.y, e.z, e.w, sc);
+        const uint32_t k = fkey(v);
+        if (act && k > kmax) kmax = k;
+        const int x = x0 - 3 + (e.x & 63), y = y0 + ((e.x >> 8) & 63);
+        bool cand = act && !(e.x & E3_Q_MAXONLY) && v > 0.f;
+        bool open = cand && !(e.x & E3_Q_DECIDED);
+#pragma unroll 1
+        for (int q = 0; q < 9 && __ballot(open); ++q) {
+            if (q == 4 || !open) continue;
+            const int i = q / 3, j = q - 3 * i;
+            int T, dd, sxy;
+            e3_sums(img, P.pitch, W, H, x - 1 + j, y - 1 + i, T, dd, sxy);
+            if (!(v >= e3_exact(T, dd, sxy, sc))) cand = open = false;
+        }
+        const uint64_t m = __ballot(cand);
+        if (m) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&P.nkeys[b], __popcll(m));
+            base = __builtin_amdgcn_readfirstlane(base) + lane_prefix(m);
+            if (cand && base < P.ccap) out[base] = ((uint64_t)k << 32) | (uint32_t)(y * W + x);
+        }
+    };
+    // empty the queue in batches while it holds `least` entries or more, then the own rows it
+    // had no room for, their box sums taken from the image (only when a few rows flag more
+    // pixels than the queue holds: periodic patterns, where most pixels tie)
+    auto service = [&](int least) {
+        for (;;) {
+            int4 e = make_int4(0, 0, 0, 0);
+            bool act;
+            if (nq >= least) {
+                wave_lds_sync();
+                const int n = nq < 64 ? nq : 64;
+                nq -= n;
+                act = lane < n;
+                e = qbuf[nq + lane];                     // nq + 64 <= E3_QCAP: inside the queue
+                wave_lds_sync();
+            } else if (ovf) {
+                const int rn = y0 + __builtin_ctzll(ovf);
+                ovf &= ovf - 1;
+                act = own;
+                if (own) {
+                    e.x = (int)cl | ((rn - y0) << 8) | (nms_col && rn >= o0 && rn < o1 ? 0 : E3_Q_MAXONLY);
+                    e3_sums(img, P.pitch, W, H, c, rn, e.y, e.z, e.w);
+                }
+            } else {
+                break;
+            }
+            batch(e, act);
+        }
+    };
+    // queue the pixels of own row rn with `q` set (box sums T, dd, sxy)
+    auto push = [&](bool q, int rn, int flags, int T, int dd, int sxy) {
+        const uint64_t m = __ballot(q);
+        const int n = nq + __popcll(m);
+        if (n <= E3_QCAP) {
+            if (q) qbuf[nq + lane_prefix(m)] = make_int4((int)cl | ((rn - y0) << 8) | flags, T, dd, sxy);
+            nq = n;
+        } else {
+            ovf |= 1ull << (rn - y0);
+        }
+    };
+    // eigen row r from the box row sums of rows r-1, r, r+1; then the NMS of row r-1.  ST: a
+    // steady-state row (r-1 is an NMS row of this tile).
+    auto eig_row = [&](int r, int ax, int ay, int az, int bx, int by, int bz, int cx, int cy, int cz, auto st) {
+        constexpr bool ST = decltype(st)::value;
         const int sxx = ax + bx + cx, sxy = ay + by + cy, syy = az + bz + cz;
         const int T = sxx + syy, dd = sxx - syy;
-        const double Dd = (double)dd * (double)dd + 4.0 * ((double)sxy * (double)sxy);
-        const float v = (float)(((double)T - sqrt_int_f64(Dd)) * sc);
-        if (own && r >= y0 && r < m1) {
-            const uint32_t k = fkey(v);
-            kmax = k > kmax ? k : kmax;
-            if (P.eig_out) P.eig_out[(int64_t)b * W * H + (int64_t)r * W + c] = v;
-        }
         const int rn = r - 1;
-        const int iV = __float_as_int(v);
-        const float mV2 = fmaxf(__int_as_float(dpp_from_left(iV)), __int_as_float(dpp_from_right(iV)));
-        if (rn >= o0 && rn < o1) {
-            const float mV = fmaxf(mV2, v);
-            const bool cand = nms_col && out && eB > 0.f && eB >= fmaxf(fmaxf(mA3, mV), mB2);
-            const uint64_t m = __ballot(cand);
-            if (m) {
-                if (cand) {
-                    const int pre = __popcll(m & ((1ull << lane) - 1ull));
-                    kbuf[nbuf + pre] = ((uint64_t)fkey(eB) << 32) | (uint32_t)(rn * W + c);
-                }
-                nbuf += __popcll(m);
-                if (nbuf > E3_CAP - 64) flush();
+        if constexpr (EXACT) {
+            const float v = e3_exact(T, dd, sxy, sc);
+            if (own && r >= y0 && r < m1) {
+                const uint32_t k = fkey(v);
+                kmax = k > kmax ? k : kmax;
+                if (P.eig_out) P.eig_out[(int64_t)b * W * H + (int64_t)r * W + c] = v;
             }
+            const float mV2 = dpp_max_lr(v);
+            if (ST || (rn >= o0 && rn < o1)) {
+                const float mV = fmaxf(mV2, v);
+                const bool cand = nms_col && out && eB > 0.f && eB >= fmaxf(fmaxf(mA3, mV), mB2);
+                const uint64_t m = __ballot(cand);
+                if (m) {
+                    if (cand) kbuf[nbuf + lane_prefix(m)] = ((uint64_t)fkey(eB) << 32) | (uint32_t)(rn * W + c);
+                    nbuf += __popcll(m);
+                    if (nbuf > E3_CAP - 64) flush();
+                }
+            }
+            mA3 = fmaxf(mB2, eB);
+            mB2 = mV2;
+            eB = v;
+        } else {
+            int lo, hi;
+            e3_interval(T, dd, sxy, scf, epk, lo, hi);
+            const int nV2 = dpp_max_lr(lo), nV2H = dpp_max_lr(hi);
+            if (ST || (rn >= o0 && rn < o1)) {
+                // a pixel of row r-1 can be a maximum only if its upper bound is positive and reaches
+                // every neighbour's lower bound (hi < a neighbour's lo means v < that neighbour's
+                // v); it is one for any v > 0 if its lower bound reaches every neighbour's upper
+                // bound.  All eight neighbours of an NMS pixel are inside the image.
+                const int nlo = max(max(nA3, max(nV2, lo)), nB2);
+                const int nhi = max(max(nA3H, max(nV2H, hi)), nB2H);
+                const bool poss = nms_col && hiB > 0 && hiB >= nlo;
+                push(poss || edge_col, rn, edge_col ? E3_Q_MAXONLY : (loB >= nhi ? E3_Q_DECIDED : 0), TB, dB, sB);
+            } else if (rn >= y0 && rn < m1) {
+                push(own, rn, E3_Q_MAXONLY, TB, dB, sB);         // image row 0
+            }
+            nA3 = max(nB2, loB);
+            nA3H = max(nB2H, hiB);
+            nB2 = nV2;
+            nB2H = nV2H;
+            loB = lo;
+            hiB = hi;
+            TB = T; dB = dd; sB = sxy;
         }
-        mA3 = fmaxf(mB2, eB);
-        mB2 = mV2;
-        eA = eB;
-        eB = v;
     };
-    // image rows are loaded E3_PF rows ahead of their use (a register ring), so the row loop
-    // does not wait a full memory round trip per row
+    // image rows are loaded E3_PF rows ahead of their use (a register ring: pf[k] holds row
+    // ir + k), so the row loop does not wait a full memory round trip per row
     constexpr int E3_PF = 8;
+    static_assert(E3_PF < VO_BORDER, "the ring reads up to E3_PF rows below the image");
+    int hsA = 0, hdA = 0, hsB = 0, hdB = 0;              // Sobel row terms of image rows ir-2, ir-1
+    int xA = 0, yA = 0, zA = 0, xB = 0, yB = 0, zB = 0;  // box row sums (xx, xy, yy) of rows pr-2, pr-1
     int pf[E3_PF];
     const int ir_end = g1 + 1;
 #pragma unroll
-    for (int k = 0; k < E3_PF; ++k) pf[k] = (g0 - 1 + k <= ir_end) ? colp[(int64_t)(g0 - 1 + k) * P.pitch] : 0;
-    // rows in groups of E3_PF, unrolled: ring slot u holds row ir0 + u, and the row registers
-    // (A / B rings) are renamed instead of moved every row
-    for (int ir0 = g0 - 1; ir0 <= ir_end; ir0 += E3_PF) {
-#pragma unroll
-    for (int u = 0; u < E3_PF; ++u) {
-        const int ir = ir0 + u;
-        if (ir > ir_end) break;
-        const int iv = pf[u];
-        pf[u] = (ir + E3_PF <= ir_end) ? colp[(int64_t)(ir + E3_PF) * P.pitch] : 0;
+    for (int k = 0; k < E3_PF; ++k) pf[k] = load_row(min(g0 - 1 + k, ir_end));
+    // image row ir (pixels iv): its Sobel row terms, the box row sums of gradient row pr = ir-1,
+    // eigen row pr-1.  ST: none of the tile's or the image's first / last rows is involved, so
+    // the row carries no test of them.
+    auto row = [&](int ir, int iv, auto st) {
+        constexpr bool ST = decltype(st)::value;
         const int il = dpp_from_left(iv), irt = dpp_from_right(iv);
         const int hs = il + 2 * iv + irt, hd = irt - il;
-        if (ir >= g0 + 1) {
+        if (ST || ir >= g0 + 1) {
             const int pr = ir - 1;                       // gradient row
             const int gx = hdA + 2 * hdB + hd, gy = hs - hsA;
             // |gx|, |gy| <= 4 * 255: 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate)
@@ -298,22 +484,79 @@ __global__ void __launch_bounds__(64) k_eig3(EigParams P)
                 if (c == W - 1) { rxx = lxx; rxy = lxy; ryy = lyy; }
             }
             const int hx = lxx + pxx + rxx, hy = lxy + pxy + rxy, hz = lyy + pyy + ryy;
-            // eigen row pr-1 (BORDER_REFLECT_101 in y: row -1 is row 1)
-            const int r = pr - 1;
-            if (r >= e0) {
-                if (r == 0) eig_row(r, hx, hy, hz, xB, yB, zB, hx, hy, hz);
-                else eig_row(r, xA, yA, zA, xB, yB, zB, hx, hy, hz);
+            const int r = pr - 1;                        // eigen row
+            if constexpr (ST) {
+                eig_row(r, xA, yA, zA, xB, yB, zB, hx, hy, hz, st);
+            } else {
+                if (r >= e0) {
+                    const bool top = r == 0;             // BORDER_REFLECT_101 in y: row -1 is row 1
+                    eig_row(r, top ? hx : xA, top ? hy : yA, top ? hz : zA, xB, yB, zB, hx, hy, hz, st);
+                }
+                if (pr == H - 1 && pr >= e0 && pr >= 1) {    // last image row: row H is row H-2
+                    eig_row(pr, xB, yB, zB, hx, hy, hz, xB, yB, zB, st);
+                    if constexpr (!EXACT)
+                        if (pr < m1) push(own, pr, E3_Q_MAXONLY, TB, dB, sB);
+                }
             }
-            if (pr == H - 1 && pr >= e0 && pr >= 1)      // last image row: row H is row H-2
-                eig_row(pr, xB, yB, zB, hx, hy, hz, xB, yB, zB);
             xA = xB; yA = yB; zA = zB;
             xB = hx; yB = hy; zB = hz;
         }
         hsA = hsB; hdA = hdB;
         hsB = hs; hdB = hd;
+    };
+    // one row with every edge test, the ring shifted by one: the tile's first and last rows
+    auto edge_row = [&](int ir) {
+        const int iv = pf[0];
+#pragma unroll
+        for (int k = 0; k + 1 < E3_PF; ++k) pf[k] = pf[k + 1];
+        pf[E3_PF - 1] = load_row(min(ir + E3_PF, ir_end));       // past the end: a row never used
+        row(ir, iv, std::false_type());
+    };
+    // steady rows [s_lo, s_hi + E3_PF): the NMS row ir-3 is an NMS row of this tile, the gradient
+    // row ir-1 is above the image's last row and ir <= ir_end, for all E3_PF rows of a group
+    const int s_lo = o0 + 3, s_hi = min(min(o1 - (E3_PF - 3), H - E3_PF), ir_end - (E3_PF - 1));
+    int ir = g0 - 1;
+    // a tile too short for one steady group runs as edge rows only.  (The steady loop is entered
+    // without a test of its own: a path around it that carries the row state costs the
+    // registers that keep 8 waves per SIMD.)
+    if (s_lo <= s_hi) {
+        for (; ir < s_lo; ++ir) edge_row(ir);            // queues one row at most (image row 0)
+        // groups of E3_PF rows, unrolled: ring slot u holds row ir + u, and the row registers
+        // (A / B rings) are renamed instead of moved every row
+        do {
+#pragma unroll
+            for (int u = 0; u < E3_PF; ++u) {
+                const int iv = pf[u];
+                pf[u] = load_row(ir + u + E3_PF);        // <= ir_end + E3_PF <= H + 8: a border row
+                row(ir + u, iv, std::true_type());
+            }
+            ir += E3_PF;
+            if constexpr (!EXACT) {
+                if (nq >= 64 || ovf) {
+                    // the ring is loaded again after the batches instead of living through them:
+                    // the batch code has the registers
+                    service(64);
+#pragma unroll
+                    for (int k = 0; k < E3_PF; ++k) pf[k] = load_row(min(ir + k, ir_end));
+                }
+            }
+        } while (ir <= s_hi);
     }
+    // the remaining rows; the interval form empties its queue as it goes, and fully at the end
+    for (;;) {
+        const bool more = ir <= ir_end;
+        if (more) edge_row(ir++);
+        if constexpr (!EXACT) {
+            if (nq >= (more ? 64 : 1) || ovf) {
+                service(more ? 64 : 1);
+#pragma unroll
+                for (int k = 0; k < E3_PF; ++k) pf[k] = load_row(min(ir + k, ir_end));
+            }
+        }
+        if (!more) break;
     }
-    if (out && nbuf) flush();
+    if constexpr (EXACT)
+        if (out && nbuf) flush();
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const uint32_t t2 = __shfl_xor(kmax, o, 64);
@@ -1255,15 +1498,19 @@ extern "C" int vo_set_gftt_select(int mode)
 }
 
 // eigen + NMS pass: the row-streaming k_eig3 for blockSize 3 / min-eigenvalue (every
-// reference configuration), the tiled k_eignms otherwise (or with VO_EIG_GENERIC=1)
+// reference configuration), the tiled k_eignms otherwise (or with VO_EIG_GENERIC=1).  k_eig3
+// decides the NMS on f32 intervals and evaluates the double expression for the possible maxima
+// only; with the eigen map asked for, no key list, or VO_EIG_EXACT=1 it evaluates every pixel.
 static void launch_eig(EigParams E, hipStream_t st)
 {
     static const int generic = vo_env_int("VO_EIG_GENERIC", 0);
+    static const int exact = vo_env_int("VO_EIG_EXACT", 0);
     if (E.bs == 3 && !E.harris && !generic) {
         E.tiles_x = (E.W + E3_OUT - 1) / E3_OUT;
         E.tiles_y = (E.H + E3_TH - 1) / E3_TH;
         const int total = E.B * E.tiles_x * E.tiles_y;
-        hipLaunchKernelGGL(k_eig3, dim3(((total + 7) / 8) * 8), dim3(64), 0, st, E);
+        if (E.eig_out || !E.keys || exact) hipLaunchKernelGGL(k_eig3<true>, dim3(((total + 7) / 8) * 8), dim3(64), 0, st, E);
+        else hipLaunchKernelGGL(k_eig3<false>, dim3(((total + 7) / 8) * 8), dim3(64), 0, st, E);
         return;
     }
     const int total = E.B * E.tiles_x * E.tiles_y;
@@ -1291,6 +1538,22 @@ extern "C" int vo_gftt_eigmap(const vo_dims* d, const vo_opts* o, const vo_state
     E.keys = nullptr; E.nkeys = nullptr; E.ccap = 0;
     E.chain_status = nullptr;
     E.eig_out = s->eig;
+    launch_eig(E, st);
+    return hip_ok() ? VO_OK : VO_EHIP;
+}
+
+extern "C" int vo_gftt_keys(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream)
+{
+    if (!d || !o || !s || cur < 0 || cur > 1) return VO_EARG;
+    if (o->feature_block_size < 1 || o->feature_block_size > EIG_MAXBS) return VO_EARG;
+    hipStream_t st = VO_STREAM(stream);
+    if (hipMemsetAsync(s->eig_max, 0, sizeof(uint32_t) * d->B, st) != hipSuccess) return VO_EHIP;
+    if (hipMemsetAsync(s->gf_n, 0, sizeof(int32_t) * d->B, st) != hipSuccess) return VO_EHIP;
+    EigParams E;
+    fill_eig(E, d, o, s, cur);
+    E.keys = s->gf_keys; E.nkeys = s->gf_n; E.ccap = d->ccap;
+    E.chain_status = s->status;
+    E.eig_out = nullptr;
     launch_eig(E, st);
     return hip_ok() ? VO_OK : VO_EHIP;
 }
