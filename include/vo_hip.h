@@ -107,7 +107,8 @@ typedef struct vo_state {
     /* scratch */
     float* trk_pts;               /* LK outputs [B][ncap+pcap][2]                        */
     uint8_t* trk_st;              /* LK status  [B][ncap+pcap]                           */
-    float* trk_err;               /* LK err     [B][ncap+pcap]                           */
+    float* trk_err;               /* LK err     [B][ncap+pcap]; written by vo_track_fb only
+                                     (vo_track / vo_track_lk leave it untouched)          */
     float* eig;                   /* GFTT eigen map [B][W*H]                              */
     uint32_t* eig_max;            /* [B] order-preserving float bits                      */
     uint64_t* gf_keys;            /* [B][ccap]                                            */
@@ -167,7 +168,9 @@ int vo_pyr_deriv(const vo_dims* d, const vo_state* s, int which, vo_stream_t str
 int vo_track(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, vo_stream_t stream);
 
 /* vo_track without the filtering: the calcOpticalFlowPyrLK calls (:281, :287) into the tracking
- * scratch (trk_pts, trk_st); vo_filter_pnp_triangulate then filters (:283-290) in its PnP block. */
+ * scratch (trk_pts, trk_st); vo_filter_pnp_triangulate then filters (:283-290) in its PnP block.
+ * Neither this nor vo_track writes trk_err: nothing in the step reads it, so the L1-error pass is
+ * not run (vo_track_fb still runs it and writes trk_err). */
 int vo_track_lk(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, vo_stream_t stream);
 
 /* PnP step (:338-358): guard N >= 8, cv2.solvePnPRansac(P3P) + EPnP refit, inlier

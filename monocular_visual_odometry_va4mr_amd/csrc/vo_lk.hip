@@ -39,7 +39,7 @@ struct LKParams {
     const int32_t* chain_status;
     float* out;
     uint8_t* st;
-    float* err;
+    float* err;                     // level 0's L1 error per point, or null: the error pass is not run
     int ocap;
     // read by the EX instantiations alone (vo_lk_points_ex, vo_lk_points_fb, vo_track_fb)
     const float* init;              // OPTFLOW_USE_INITIAL_FLOW: [B][ocap][2], the estimate's start at level L (or null)
@@ -374,6 +374,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                     status = 0;
                     break;
                 }
+                if (!P.err) break;              // nobody reads the error; the status decision above stays
                 const float aa = fx - inx, cc = fy - iny;
                 iw00 = __float2int_rn((1.f - aa) * (1.f - cc) * (float)(1 << 14));
                 iw01 = __float2int_rn(aa * (1.f - cc) * (float)(1 << 14));
@@ -460,7 +461,9 @@ __device__ long long g_lkprof[VO_MAX_LEVELS][1024][8];
 // may run up to 3 bytes past a row end (next row, or the >= 64-byte tail slack that the
 // caller must leave after each pyramid -- launch_lk checks it).  Arithmetic is identical to
 // k_lk (bit-exact with the CPU restatement).
-template <int WW, int WH, bool EX = false>
+// ERR (the instantiations without EX; EX decides by P.err at run time): the level-0 L1-error pass
+// exists only where the caller gave an err buffer.  Its bounds test is a status decision and stays.
+template <int WW, int WH, bool EX = false, bool ERR = true>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_lk_w(LKParams P, int level_hi, int level_lo, int B, int nb, int xcd)
 {
     constexpr int WPB = 1;
@@ -889,6 +892,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
                         status = 0;
                         break;
                     }
+                    // the pass itself (restage, taps, reduction) only where err is wanted
+                    if (EX ? !P.err : !ERR) break;
                     if ((unsigned)(inx - tx0) > 2u * LK_M || (unsigned)(iny - ty0) > 2u * LK_M) stage_j(inx, iny);
                     const float aa = fx - inx, cc = fy - iny;
                     const int w00 = __float2int_rn((1.f - aa) * (1.f - cc) * (float)(1 << 14));
@@ -925,7 +930,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
                     }
                 }
                 P.st[oidx] = (uint8_t)status;
-                if (P.err) P.err[oidx] = errv;
+                if ((EX || ERR) && P.err) P.err[oidx] = errv;
             }
         }
     }
@@ -1007,7 +1012,9 @@ static int launch_lk_t(const LKParams& P, int B, hipStream_t st)
     // sizes (cv2.calcOpticalFlowPyrLK's default 21x21 on the cv2compat surface): k_lk, one
     // launch per level.
     if (staged15) {
-        hipLaunchKernelGGL((k_lk_w<15, 15, EX>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
+        // without EX the error pass is compiled in only for a caller that gave an err buffer
+        if (EX || P.err) hipLaunchKernelGGL((k_lk_w<15, 15, EX>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
+        else hipLaunchKernelGGL((k_lk_w<15, 15, false, false>), dim3(nblk), dim3(64), 0, st, P, L, 0, B, nb, xcd_env);
         return hip_ok() ? VO_OK : VO_EHIP;
     }
     // a side beyond the materialised border: the instantiations that reflect every tap
@@ -1045,12 +1052,13 @@ static bool lk_thr_ok(double thr) { return thr > 0. && thr <= DBL_MAX; }   // fa
 
 // the engine's points: tracked landmarks, then the candidates where a chain has more than one
 // (:286 "if P > 1"), into the tracking scratch
-static void lk_state_segments(LKParams& P, const vo_dims* d, const vo_state* s)
+// (nothing in the step reads the L1 error, so only vo_track_fb, whose callers may, asks for it)
+static void lk_state_segments(LKParams& P, const vo_dims* d, const vo_state* s, float* err)
 {
     P.p0 = s->lm_kp; P.n0 = s->nL; P.cap0 = d->ncap;
     P.p1 = s->c_kp; P.n1 = s->nC; P.cap1 = d->pcap; P.seg1_min = 1;
     P.chain_status = s->status;
-    P.out = s->trk_pts; P.st = s->trk_st; P.err = s->trk_err; P.ocap = d->ncap + d->pcap;
+    P.out = s->trk_pts; P.st = s->trk_st; P.err = err; P.ocap = d->ncap + d->pcap;
 }
 
 // the caller's points: one segment of cap points per chain, every chain tracked
@@ -1098,7 +1106,7 @@ extern "C" int vo_track_fb(const vo_dims* d, const vo_opts* o, const vo_state* s
     if (!d || !o || !s || prev < 0 || prev > 1 || !scratch || !lk_thr_ok(fb_threshold)) return VO_EARG;
     LKParams P;
     fill_lk(P, d, o, s, prev);
-    lk_state_segments(P, d, s);
+    lk_state_segments(P, d, s, s->trk_err);      // the one entry that still writes trk_err
     int rc = launch_lk(P, d->B, VO_STREAM(stream));
     if (rc) return rc;
     rc = launch_lk_back(P, d, o, s, prev, fb_threshold, scratch, VO_STREAM(stream));
@@ -1112,7 +1120,7 @@ extern "C" int vo_track_lk(const vo_dims* d, const vo_opts* o, const vo_state* s
     if (!d || !o || !s || prev < 0 || prev > 1) return VO_EARG;
     LKParams P;
     fill_lk(P, d, o, s, prev);
-    lk_state_segments(P, d, s);
+    lk_state_segments(P, d, s, nullptr);
     return launch_lk(P, d->B, VO_STREAM(stream));
 }
 

@@ -231,7 +231,7 @@ class Engine:
         T["status"] = z(B, dt=torch.int32)
         T["trk_pts"] = z(B, ncap + pcap, 2, dt=torch.float32)
         T["trk_st"] = z(B, ncap + pcap, dt=torch.uint8)
-        T["trk_err"] = z(B, ncap + pcap, dt=torch.float32)
+        T["trk_err"] = z(B, ncap + pcap, dt=torch.float32)      # written by vo_track_fb only
         T["eig"] = z(B, self.W * self.H, dt=torch.float32)
         T["eig_max"] = z(B, dt=torch.int32)
         T["gf_keys"] = z(B, d.ccap, dt=torch.int64)

@@ -7,8 +7,8 @@ Runs bench.py's headline workload (768 C2 chains in 2 stream groups, concurrent 
 with the library VO_HIP_LIB names, compares the 255 chains that coincide with the 256-shard
 reference cut pose by pose (bench.Headline.vs_reference) and prints one JSON line.  With
 --detail and a difference, the run is repeated up to the earliest differing pose and that
-step's tracking output (trk_pts / trk_st / trk_err of the chain, as the step's LK launch left
-it) is compared point by point with the CPU restatement's calcOpticalFlowPyrLK on the same
+step's tracking output (trk_pts / trk_st of the chain, as the step's LK launch left it; the step
+does not write trk_err) is compared point by point with the CPU restatement's calcOpticalFlowPyrLK on the same
 frames and points (diagnostics; the oracle is the checker here)."""
 import argparse
 import json
@@ -43,7 +43,7 @@ def run(steps, stop_before=None, chain=None):
             torch.cuda.synchronize()
             n = sum(len(p) for p in pts)
             snap = {"pts": np.concatenate(pts), "n_lm": nL, "trk": e.t["trk_pts"][b, :n].cpu().numpy(),
-                    "st": e.t["trk_st"][b, :n].cpu().numpy(), "err": e.t["trk_err"][b, :n].cpu().numpy(),
+                    "st": e.t["trk_st"][b, :n].cpu().numpy(),
                     "prev": hl.frames[1 + j, chain].cpu().numpy(), "cur": hl.frames[2 + j, chain].cpu().numpy()}
             break
         hl.step(2 + j)
@@ -76,21 +76,20 @@ def main():
             from oracle import _olib as O
             opts, _, _ = Op.get("kitti")
             hl, snap = run(a.steps, stop_before=j, chain=d0["chain"])
-            ro, rs, re_ = O.lk(snap["prev"], snap["cur"], snap["pts"], tuple(opts["winSize"]), opts["maxLevel"],
+            ro, rs, _ = O.lk(snap["prev"], snap["cur"], snap["pts"], tuple(opts["winSize"]), opts["maxLevel"],
                                opts["criteria"])
             dp = ~np.all(ro == snap["trk"], axis=1)
             ds = rs != snap["st"]
-            de = re_ != snap["err"]
-            bad = np.nonzero(dp | ds | de)[0]
+            bad = np.nonzero(dp | ds)[0]
             out["lk_vs_oracle"] = {
                 "points": int(len(ro)), "landmarks": snap["n_lm"], "pts_differ": int(dp.sum()),
-                "status_differ": int(ds.sum()), "err_differ": int(de.sum()),
+                "status_differ": int(ds.sum()),
                 "first": [{"i": int(i), "in": snap["pts"][i].tolist(), "gpu": snap["trk"][i].tolist(),
-                           "oracle": ro[i].tolist(), "gpu_st": int(snap["st"][i]), "oracle_st": int(rs[i]),
-                           "gpu_err": float(snap["err"][i]), "oracle_err": float(re_[i])} for i in bad[:12]]}
+                           "oracle": ro[i].tolist(), "gpu_st": int(snap["st"][i]), "oracle_st": int(rs[i])}
+                          for i in bad[:12]]}
             np.savez_compressed(os.path.join(ROOT, "gpurun_out", "lk_variant_case.npz"), prev=snap["prev"],
                                 cur=snap["cur"], pts=snap["pts"], gpu=snap["trk"], gpu_st=snap["st"],
-                                gpu_err=snap["err"], oracle=ro, oracle_st=rs, oracle_err=re_)
+                                oracle=ro, oracle_st=rs)
     print(json.dumps(out), flush=True)
 
 
