@@ -590,8 +590,12 @@ struct SelParams {
     const int32_t* chain_status;
 };
 
-// A grid cell holds up to two accepted-corner indices (u16 each, 0xFFFF = empty); the
-// geometric bound (cell = round(minDistance) <= minDistance + 0.5) allows at most two.
+// A grid cell holds two accepted-corner indices (u16 each, 0xFFFF = empty, the low slot filled
+// first); a third corner of the cell is chained to the high slot's corner in nxt3[] (u16 per
+// accepted corner, 0xFFFF = none).  Three is the most: a cell spans cs - 1 <= minDistance - 0.5
+// pixels (cs = round(minDistance)), three lattice points pairwise >= minDistance apart fit such a
+// square once 1.035 * (cs - 1) >= minDistance (from minDistance 15.5; (16,16) (31,20) (20,31)),
+// four need a side >= minDistance.
 VO_DEV uint32_t cell_get(bool lds, uint32_t* lg, uint32_t* gg, int c)
 {
     // the L2 copy is only written by atomics: read it at agent scope (past the CU's L1)
@@ -607,6 +611,36 @@ VO_DEV void cell_set(bool lds, uint32_t* lg, uint32_t* gg, int c, uint32_t v)
 {
     if (lds) lg[c] = v;
     else atomicExch(&gg[c], v);
+}
+// visit(id) for every accepted corner of a cell value
+template <class F>
+VO_DEV void cell_each(uint32_t cv, const uint16_t* nxt3, F&& visit)
+{
+    const uint32_t a = cv & 0xFFFFu, b = cv >> 16;
+    if (a == 0xFFFFu) return;
+    visit(a);
+    if (b == 0xFFFFu) return;
+    visit(b);
+    const uint32_t c = nxt3[b];
+    if (c != 0xFFFFu) visit(c);
+}
+// accepted corner `pos` into its cell; slot order inside a cell is irrelevant.  Several threads
+// may insert into one cell at once: the first two take the slots by CAS, the third finds both
+// taken (they never change again) and chains itself to the high slot's corner.
+VO_DEV void cell_insert(bool lds, uint32_t* lg, uint32_t* gg, uint16_t* nxt3, int cell, int pos)
+{
+    uint32_t cur = cell_get(lds, lg, gg, cell);
+    for (;;) {
+        if ((cur >> 16) != 0xFFFFu) {
+            nxt3[cur >> 16] = (uint16_t)pos;
+            return;
+        }
+        const uint32_t nv = ((cur & 0xFFFFu) == 0xFFFFu) ? ((cur & 0xFFFF0000u) | (uint32_t)pos)
+                                                        : ((cur & 0xFFFFu) | ((uint32_t)pos << 16));
+        const uint32_t prev = lds ? atomicCAS(&lg[cell], cur, nv) : atomicCAS(&gg[cell], cur, nv);
+        if (prev == cur) return;
+        cur = prev;
+    }
 }
 
 // hist[dgt] += 1 for every lane with `on` (12-bit digits), as one LDS atomic per distinct digit
@@ -643,7 +677,7 @@ template <int NT>
 __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
 {
     // dynamic LDS sized by the host (vo_gftt): page | candidate xy | accepted xy | grid + cell
-    // heads (if they fit) | two conflict slots per candidate
+    // heads (if they fit) | two conflict slots per candidate | third-corner links of the cells
     extern __shared__ uint64_t sel_dyn[];
     uint64_t* page = sel_dyn;
     uint32_t* cand_xy = (uint32_t*)(sel_dyn + PAGE);
@@ -653,6 +687,7 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
     // each candidate's first two earlier conflicts, in LDS (most have at most two); the rest of
     // its list (up to CONF_K) is in the per-chain global scratch
     uint16_t* cf2 = (uint16_t*)(head + P.grid_lds);
+    uint16_t* nxt3 = cf2 + 2 * PAGE;
     __shared__ uint32_t round_xy[64];
     __shared__ int sh_int[16];
     __shared__ int sh_scan[16];
@@ -711,6 +746,7 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
         for (int q = tid; q < gw * gh; q += blockDim.x) cell_set(lds, lgrid, gg, q, 0xFFFFFFFFu);
         if (par && !lds)
             for (int q = tid; q < gw * gh; q += blockDim.x) atomicExch(&ghead[q], -1);
+        for (int q = tid; q < P.acc_lds; q += blockDim.x) nxt3[q] = 0xFFFFu;
     }
     float* out = P.corners + (int64_t)b * P.mcap * 2;
     int nacc = 0;
@@ -851,15 +887,12 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
                     const int x2 = min(xc + 1, gw - 1), y2 = min(yc + 1, gh - 1);
                     for (int yy = y1; yy <= y2; ++yy)
                         for (int xx = x1; xx <= x2; ++xx) {
-                            const uint32_t cv = cell_get(lds, lgrid, gg, yy * gw + xx);
-                            for (int q = 0; q < 2; ++q) {
-                                const uint32_t id = (cv >> (16 * q)) & 0xFFFFu;
-                                if (id == 0xFFFFu) break;
+                            cell_each(cell_get(lds, lgrid, gg, yy * gw + xx), nxt3, [&](uint32_t id) {
                                 const uint32_t aa = acc_xy[id];
                                 const float ddx = (float)x - (float)(aa & 0xFFFF);
                                 const float ddy = (float)y - (float)(aa >> 16);
                                 if ((double)(ddx * ddx + ddy * ddy) < md2) rej = true;
-                            }
+                            });
                         }
                 }
                 stt[i] = rej ? 2 : 0;                             // 0 undecided, 1 accepted, 2 rejected
@@ -903,9 +936,11 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
             };
             // each candidate's earlier conflicts (same test as OpenCV's walk), found once:
             // count in LDS, indices in the per-chain scratch (the eigen-map buffer, unused on
-            // this path); more than CONF_K conflicts -> rescan the cells in every round
+            // this path); more than CONF_K conflicts, or a candidate past the lists the scratch
+            // has room for (an image of fewer than 8 * PAGE pixels) -> rescan the cells in every round
             constexpr int CONF_K = 16;
             uint16_t* conf = (uint16_t*)(P.gscratch + (int64_t)b * P.gstride);
+            const int conf_cap = (int)min((int64_t)PAGE, P.gstride * 2 / CONF_K);
             uint8_t* ncf = (uint8_t*)(nxt + PAGE) + PAGE;          // PAGE bytes after stt
             for (int i = tid; i < take; i += blockDim.x) {
                 if (stt[i] != 0) { ncf[i] = 0; continue; }
@@ -924,12 +959,12 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
                             const float ddy = (float)y - (float)(aa >> 16);
                             if ((double)(ddx * ddx + ddy * ddy) < md2) {
                                 if (c < 2) cf2[2 * i + c] = (uint16_t)j;
-                                if (c < CONF_K) conf[(int64_t)i * CONF_K + c] = (uint16_t)j;
+                                if (c < CONF_K && i < conf_cap) conf[(int64_t)i * CONF_K + c] = (uint16_t)j;
                                 ++c;
                             }
                             return false;
                         });
-                ncf[i] = (uint8_t)min(c, 255);
+                ncf[i] = (uint8_t)((c > 2 && i >= conf_cap) ? 255 : min(c, 255));
             }
             __syncthreads();
             SELPROF(5);
@@ -1000,16 +1035,7 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
                     acc_xy[pos] = xy;
                     out[2 * pos] = (float)x;
                     out[2 * pos + 1] = (float)y;
-                    // at most two corners share a cell; slot order inside a cell is irrelevant
-                    const int cell = (y / cs) * gw + (x / cs);
-                    uint32_t cur = cell_get(lds, lgrid, gg, cell);
-                    for (;;) {
-                        const uint32_t nv = ((cur & 0xFFFFu) == 0xFFFFu) ? ((cur & 0xFFFF0000u) | (uint32_t)pos)
-                                                                        : ((cur & 0xFFFFu) | ((uint32_t)pos << 16));
-                        const uint32_t prev = lds ? atomicCAS(&lgrid[cell], cur, nv) : atomicCAS(&gg[cell], cur, nv);
-                        if (prev == cur) break;
-                        cur = prev;
-                    }
+                    cell_insert(lds, lgrid, gg, nxt3, (y / cs) * gw + (x / cs), pos);
                 }
                 nacc = min(nacc + tot, limit);
             }
@@ -1046,15 +1072,12 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
                         const int x2 = min(xc + 1, gw - 1), y2 = min(yc + 1, gh - 1);
                         for (int yy = y1; yy <= y2 && tent; ++yy)
                             for (int xx = x1; xx <= x2 && tent; ++xx) {
-                                const uint32_t cv = cell_get(lds, lgrid, gg, yy * gw + xx);
-                                for (int q = 0; q < 2; ++q) {
-                                    const uint32_t id = (cv >> (16 * q)) & 0xFFFFu;
-                                    if (id == 0xFFFFu) break;
+                                cell_each(cell_get(lds, lgrid, gg, yy * gw + xx), nxt3, [&](uint32_t id) {
                                     const uint32_t a = acc_xy[id];
                                     const float ddx = (float)x - (float)(a & 0xFFFF);
                                     const float ddy = (float)y - (float)(a >> 16);
-                                    if ((double)(ddx * ddx + ddy * ddy) < md2) { tent = false; break; }
-                                }
+                                    if ((double)(ddx * ddx + ddy * ddy) < md2) tent = false;
+                                });
                             }
                     }
                     const uint64_t tmask = __ballot(tent);
@@ -1103,18 +1126,7 @@ __global__ void __launch_bounds__(NT) k_gftt_select(SelParams P)
                         acc_xy[idx] = (uint32_t)x | ((uint32_t)y << 16);
                         out[2 * idx] = (float)x;
                         out[2 * idx + 1] = (float)y;
-                        if (use_grid) {
-                            // at most two corners share a cell; slot order inside a cell is irrelevant
-                            const int cell = yc * gw + xc;
-                            uint32_t cur = cell_get(lds, lgrid, gg, cell);
-                            for (;;) {
-                                const uint32_t nv = ((cur & 0xFFFFu) == 0xFFFFu) ? ((cur & 0xFFFF0000u) | (uint32_t)idx)
-                                                                                : ((cur & 0xFFFFu) | ((uint32_t)idx << 16));
-                                const uint32_t prev = lds ? atomicCAS(&lgrid[cell], cur, nv) : atomicCAS(&gg[cell], cur, nv);
-                                if (prev == cur) break;
-                                cur = prev;
-                            }
-                        }
+                        if (use_grid) cell_insert(lds, lgrid, gg, nxt3, yc * gw + xc, idx);
                     }
                     nacc += nnew;
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1629,10 +1641,11 @@ extern "C" int vo_gftt(const vo_dims* d, const vo_opts* o, const vo_state* s, in
         S.grid_lds = cells <= GRID_LDS_CELLS ? (int)cells : 0;
         // grid + per-cell candidate lists in LDS when they fit, else in the eigen-map scratch
         // (after the conflict lists) for the same parallel walk, else the wave-serial L2 path
-        if (16 * (size_t)PAGE + 4 * (size_t)S.acc_lds + 8 * (size_t)S.grid_lds > 150 * 1024) S.grid_lds = 0;
+        if (16 * (size_t)PAGE + 6 * (size_t)S.acc_lds + 8 * (size_t)S.grid_lds > 150 * 1024) S.grid_lds = 0;
         static const int noglb = vo_env_int("VO_SEL_SERIAL_L2", 0);
         S.grid_glb = !noglb && S.grid_lds == 0 && SEL_GG_OFF + 2 * cells <= S.gstride;
-        const size_t lds = 16 * (size_t)PAGE + 4 * (size_t)S.acc_lds + 8 * (size_t)S.grid_lds;
+        // page, candidate xy and conflict slots | accepted xy + third-corner links | grid + heads
+        const size_t lds = 16 * (size_t)PAGE + 6 * (size_t)S.acc_lds + 8 * (size_t)S.grid_lds;
         static const bool attr_ok =
             hipFuncSetAttribute((const void*)k_gftt_select<SEL_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 150 * 1024) == hipSuccess &&

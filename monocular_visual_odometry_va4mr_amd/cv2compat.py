@@ -106,6 +106,10 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, mask=None,
     if st != 0:
         raise error(L.STATUS_NAMES.get(st, str(st)))
     n = int(eng.t["nCorners"][0])
+    if n < 0:
+        # more corners than the engine holds (maxCorners <= 0 and more than its 8192): the selection
+        # reports it instead of truncating, as a chain's step does with VO_ST_CAPACITY
+        raise error(L.STATUS_NAMES[L.ST_CAPACITY])
     if n == 0:
         return None
     return eng.t["corners"][0, :n].cpu().numpy().reshape(-1, 1, 2).copy()

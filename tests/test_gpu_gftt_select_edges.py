@@ -1,0 +1,130 @@
+"""GFTT corner selection, both forms (the one-block k_gftt_select and the split k_gsel_*), on the
+cases of gftt_cases.py: three accepted corners in one grid cell, long runs of exactly equal
+eigenvalues, grids with one row / one column / ragged edges, half-integer minDistance, the limits of
+the split form and maxCorners of 1 and <= 0 (test_gftt_cases_ref.py shows on the CPU what each case
+reaches).  The corner list and its length are those of the oracle's goodFeaturesToTrack, bit for bit.
+
+vo_set_gftt_select(1 | 2) pins the form; where the split form does not apply (gftt_cases.split_applies)
+both modes run the one-block kernel and are seen to agree there.
+"""
+import numpy as np
+import pytest
+
+import gftt_cases as GC
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+SENT = -7.0
+_ENGINES = {}
+
+
+@pytest.fixture
+def sel_mode():
+    from monocular_visual_odometry_va4mr_amd import _lib as L
+
+    def set_(m):
+        L.check(L.lib().vo_set_gftt_select(int(m)), "vo_set_gftt_select")
+    yield set_
+    set_(0)
+
+
+def _engine(W, H, B=1):
+    """one engine per size with the largest corner capacity; the cases set its detector options"""
+    from monocular_visual_odometry_va4mr_amd.engine import Engine
+    from monocular_visual_odometry_va4mr_amd import options as O
+    if (W, H, B) not in _ENGINES:
+        opts, _, _ = O.get("kitti")
+        opts.update(feature_max_corners=GC.MC)
+        _ENGINES[W, H, B] = Engine(np.eye(3), opts, W, H, batch=B, ncap=256, pcap=256, fcap=4)
+    eng = _ENGINES[W, H, B]
+    assert eng.dims.mcap == GC.MC
+    return eng
+
+
+def _select(eng, frames, q, md, mc):
+    """vo_gftt on `frames` with the corner buffer pre-filled: [(corners, nCorners)] per chain, gf_n"""
+    eng.opts.feature_quality_level = float(q)
+    eng.opts.feature_min_dist = float(md)
+    eng.opts.feature_max_corners = int(mc)
+    eng.build_pyramid(frames, 0)
+    eng.t["corners"].fill_(SENT)
+    eng.t["nCorners"].fill_(-5)
+    assert eng.lib.vo_gftt(eng._pd, eng._po, eng._ps, 0, eng.stream) == 0
+    torch.cuda.synchronize()
+    assert not eng.t["status"].any()
+    corners = eng.t["corners"].cpu().numpy()
+    ns = eng.t["nCorners"].cpu().numpy()
+    out = []
+    for b in range(eng.B):
+        n = int(ns[b])
+        assert 0 <= n <= eng.dims.mcap, f"chain {b}: nCorners {n}"
+        assert (corners[b, n:] == SENT).all(), f"chain {b}: rows past nCorners written"
+        out.append((corners[b, :n], n))
+    return out, eng.t["gf_n"].cpu().numpy().copy()
+
+
+@pytest.mark.parametrize("name", list(GC.cases()))
+def test_case_both_forms_match_oracle(sel_mode, name):
+    img, q, md, mc = GC.cases()[name]
+    ref = GC.expect(name)
+    H, W = img.shape
+    eng = _engine(W, H)
+    passing = {}
+    for mode in (1, 2):
+        sel_mode(mode)
+        for rep in range(2):              # the split form must find its scratch zeroed by the call before
+            ((got, n),), gf_n = _select(eng, img, q, md, mc)
+            print(f"{name} mode {mode} call {rep}: {n} corners, oracle {len(ref)}, gf_n {int(gf_n[0])}")
+            assert n == len(ref) and np.array_equal(got, ref), f"{name} mode {mode} call {rep}: {n} vs {len(ref)}"
+            passing[mode, rep] = int(gf_n[0])
+    assert len(set(passing.values())) == 1, f"{name}: passing-key counts {passing}"
+    assert passing[1, 0] == len(GC.passing_keys(img, q)[0])
+
+
+def test_four_mixed_chains_both_forms(sel_mode):
+    """three_in_cell_md40, checker4, a flat frame and a crop in one launch, then in reversed chain
+    order: a chain's grid, conflict-list and histogram scratch must not leak into its neighbour"""
+    from oracle import _olib as O
+    W, H = 320, 240
+    q, md, mc = GC.THREE_QUALITY, 40.0, GC.MC
+    frames = [GC.cases()["three_in_cell_md40"][0], GC.checker4(), np.full((H, W), 77, np.uint8), GC.crop(W, H)]
+    refs = [GC.expect("three_in_cell_md40"), GC.expect("checker4_md40"), O.gftt(frames[2], mc, q, md),
+            O.gftt(frames[3], mc, q, md)]
+    assert len(refs[2]) == 0 and len(refs[3]) > 3
+    eng = _engine(W, H, B=4)
+    passing = {}
+    for mode in (2, 1):
+        sel_mode(mode)
+        for order in ([0, 1, 2, 3], [3, 2, 1, 0], [1, 0, 3, 2]):
+            out, gf_n = _select(eng, np.stack([frames[i] for i in order]), q, md, mc)
+            for b, i in enumerate(order):
+                got, n = out[b]
+                assert n == len(refs[i]) and np.array_equal(got, refs[i]), \
+                    f"mode {mode} order {order} chain {b} (frame {i}): {n} vs {len(refs[i])}"
+                passing.setdefault(i, set()).add(int(gf_n[b]))
+    assert all(len(v) == 1 for v in passing.values()), f"passing-key counts {passing}"
+
+
+@pytest.mark.parametrize("name,md", [("three_in_cell_md40", 40.0), ("checker4_md2", 2)])
+def test_cv2compat_unlimited_corners(name, md):
+    """cv2compat.goodFeaturesToTrack with maxCorners = 0 (the one-block form at the engine's capacity)"""
+    from monocular_visual_odometry_va4mr_amd import cv2compat
+    from oracle import _olib as O
+    img, q, _, _ = GC.cases()[name]
+    ref = O.gftt(img, 0, q, md)
+    assert np.array_equal(ref, GC.expect(name))             # fewer than the capacity: the same list
+    got = cv2compat.goodFeaturesToTrack(img, 0, q, md)
+    assert got.dtype == np.float32 and got.shape == (len(ref), 1, 2), f"{got.shape[0]} vs {len(ref)}"
+    assert np.array_equal(got[:, 0, :], ref)
+
+
+def test_cv2compat_capacity_overflow_raises():
+    """maxCorners = 0 and more corners than an engine holds: an error naming the capacity status, never
+    the buffer minus its last row (test_gftt_cases_ref.py checks the oracle's count)"""
+    from monocular_visual_odometry_va4mr_amd import cv2compat
+    from monocular_visual_odometry_va4mr_amd import _lib as L
+    img, q, md = GC.capacity_case()
+    with pytest.raises(cv2compat.error, match=L.STATUS_NAMES[L.ST_CAPACITY]):
+        cv2compat.goodFeaturesToTrack(img, 0, q, md)
