@@ -194,6 +194,27 @@ int vo_filter_pnp_triangulate(const vo_dims* d, const vo_opts* o, const vo_state
 /* cv2.goodFeaturesToTrack (:256) on pyramid level 0 of pyr[cur] -> state->corners. */
 int vo_gftt(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream);
 
+/* vo_gftt with goodFeaturesToTrack's mask argument (OpenCV 4.6 featureselect.cpp; no reference
+ * counterpart: the reference never passes one, :256).  mask: [B] images of H rows, u8, rows
+ * mask_pitch bytes apart (mask_pitch >= W, else VO_EARG with nothing launched), chains mask_stride
+ * bytes apart; a non-zero byte allows its pixel, any non-zero value counts.
+ *   - the maximum that feature_quality_level scales is taken over the allowed pixels only
+ *     (minMaxLoc(eig, ..., mask)), the allowed pixels of the image border included;
+ *   - the 3x3 local-maximum test is vo_gftt's and looks at all eight neighbours whether they are
+ *     allowed or not (dilate runs on the unmasked map): an allowed pixel beside a stronger
+ *     masked-out pixel is no corner;
+ *   - only an allowed interior pixel that passes that test becomes a corner candidate;
+ *   - the sort, its tie order, the minDistance walk, feature_max_corners and the capacity flag are
+ *     vo_gftt's.  A mask with no allowed pixel gives nCorners = 0.
+ * mask == NULL is vo_gftt itself (the other two arguments are then ignored).  A chain whose status
+ * is not 0 is skipped.  Both selection forms apply, chosen as in vo_gftt.  With a mask the eigen
+ * pass evaluates every pixel exactly (vo_gftt's interval form finds the maximum among the local
+ * maxima of the map, and the greatest allowed pixel need not be one).  Asynchronous, no host
+ * synchronisation; the mask is only read.  Replay from a captured graph has not been verified for
+ * masked calls. */
+int vo_gftt_masked(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, const uint8_t* mask,
+                   int64_t mask_stride, int32_t mask_pitch, vo_stream_t stream);
+
 /* vo_corner_subpix on state->corners / nCorners after vo_gftt, reading level 0 of pyr[cur] (no
  * reference counterpart: the reference adds goodFeaturesToTrack's integer positions, :256-268;
  * engine option feature_subpix_win).  Same limits, VO_EARG with nothing launched outside them.  A

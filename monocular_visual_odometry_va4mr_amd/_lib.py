@@ -145,6 +145,7 @@ def _declare(L):
         "vo_pnp_triangulate": ([D, O, S, P], C.c_int),
         "vo_filter_pnp_triangulate": ([D, O, S, P], C.c_int),
         "vo_gftt": ([D, O, S, C.c_int, P], C.c_int),
+        "vo_gftt_masked": ([D, O, S, C.c_int, P, i64, i32, P], C.c_int),
         "vo_gftt_eigmap": ([D, O, S, C.c_int, P], C.c_int),
         "vo_gftt_keys": ([D, O, S, C.c_int, P], C.c_int),
         "vo_gftt_subpix": ([D, S, C.c_int, i32, i32, i32, i32, i32, f64, P], C.c_int),

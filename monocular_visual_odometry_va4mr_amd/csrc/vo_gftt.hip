@@ -28,6 +28,27 @@ struct EigParams {
     const int32_t* chain_status;
     float* eig_out;          // optional [B][W*H] eigen map (diagnostics, vo_gftt_eigmap)
 };
+// the masked kernels' arguments (vo_gftt_masked): the detector mask, [B] images of H rows, u8,
+// non-zero = allowed.  It gates what counts in the per-chain maximum and what is emitted as a key;
+// the 3x3 test looks at all eight neighbours whether they are allowed or not (featureselect.cpp:
+// minMaxLoc takes the mask, dilate does not).  The unmasked kernels keep EigParams, and with it
+// the code they had.
+struct EigParamsM : EigParams {
+    const uint8_t* mask;
+    int64_t mstride;
+    int mpitch;
+};
+template <bool MASKED> using EigArgs = std::conditional_t<MASKED, EigParamsM, EigParams>;
+template <bool MASKED> VO_DEV const uint8_t* eig_mask(const EigArgs<MASKED>& P, int b)
+{
+    if constexpr (MASKED) return P.mask + (int64_t)b * P.mstride;
+    else return nullptr;
+}
+template <bool MASKED> VO_DEV int eig_mpitch(const EigArgs<MASKED>& P)
+{
+    if constexpr (MASKED) return P.mpitch;
+    else return 0;
+}
 
 // Fused cornerMinEigenVal / cornerHarris + 3x3 local-maximum test of goodFeaturesToTrack
 // (featureselect.cpp, corner.cpp) on a 64x16 output tile.
@@ -46,7 +67,8 @@ struct EigParams {
 #define EIG_MAXBS 7
 #define EIG_CW (EIG_TW + 2 + EIG_MAXBS - 1)
 #define EIG_CH (EIG_TH + 2 + EIG_MAXBS - 1)
-__global__ void __launch_bounds__(256) k_eignms(EigParams P)
+template <bool MASKED>
+__global__ void __launch_bounds__(256) k_eignms(EigArgs<MASKED> P)
 {
     __shared__ int sdx[EIG_CW * EIG_CH];
     __shared__ int sdy[EIG_CW * EIG_CH];
@@ -65,6 +87,8 @@ __global__ void __launch_bounds__(256) k_eignms(EigParams P)
     const int ew = EIG_TW + 2, eh = EIG_TH + 2;          // eig region: tile + 1-px halo
     const int cw = ew + bs - 1, ch = eh + bs - 1;        // covariance region
     const uint8_t* img = P.pyr + b * P.pstride + P.off;
+    const uint8_t* mk = eig_mask<MASKED>(P, b);
+    const int mpitch = eig_mpitch<MASKED>(P);
     if (threadIdx.x == 0) smax = 0;
     for (int q = threadIdx.x; q < cw * ch; q += blockDim.x) {
         const int qy = q / cw, qx = q - qy * cw;
@@ -105,7 +129,7 @@ __global__ void __launch_bounds__(256) k_eignms(EigParams P)
         const int x = x0 - 1 + ex, y = y0 - 1 + ey;
         if (ex >= 1 && ex <= EIG_TW && ey >= 1 && ey <= EIG_TH && x < P.W && y < P.H) {
             const uint32_t k = fkey(v);
-            lmax = k > lmax ? k : lmax;
+            if (!MASKED || mk[(int64_t)y * mpitch + x]) lmax = k > lmax ? k : lmax;
             if (P.eig_out) P.eig_out[(int64_t)b * P.W * P.H + (int64_t)y * P.W + x] = v;
         }
     }
@@ -131,7 +155,7 @@ __global__ void __launch_bounds__(256) k_eignms(EigParams P)
         const int ly = k / EIG_TW, lx = k - ly * EIG_TW;
         const int x = x0 + lx, y = y0 + ly;
         kk[j] = 0;
-        if (x >= 1 && x < P.W - 1 && y >= 1 && y < P.H - 1) {
+        if (x >= 1 && x < P.W - 1 && y >= 1 && y < P.H - 1 && (!MASKED || mk[(int64_t)y * mpitch + x])) {
             const float* r = sE + ly * ew + lx;      // row above, centred at lx+1
             const float v = r[ew + 1];
             if (v > 0.f && v >= r[0] && v >= r[1] && v >= r[2] && v >= r[ew] && v >= r[ew + 2] &&
@@ -277,10 +301,19 @@ VO_DEV void e3_sums(const uint8_t* img, int pitch, int W, int H, int x, int y, i
     dd = sxx - syy;
 }
 
+//
+// MASKED (vo_gftt_masked), exact-everywhere form only: one mask byte per lane and eigen row, used in
+// two places.  The per-chain maximum is the one over the allowed pixels, so a masked-out pixel
+// never counts in it; and only an allowed pixel is emitted as a key.  The NMS itself keeps looking
+// at all eight neighbours.  (The interval form finds the maximum among the possible local maxima
+// of the map; the greatest allowed pixel need not be one, its stronger neighbours may all be
+// masked out, so masked calls take the form that evaluates every pixel.)
+//
 // 8 waves per SIMD (64 VGPRs): the kernel hides its latencies with occupancy, and rides beside LK
-template <bool EXACT>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_eig3(EigParams P)
+template <bool EXACT, bool MASKED = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_eig3(EigArgs<MASKED> P)
 {
+    static_assert(EXACT || !MASKED, "the mask is implemented in the exact-everywhere form");
     __shared__ uint64_t kbuf[EXACT ? E3_CAP : 1];
     __shared__ int4 qbuf[EXACT ? 1 : E3_QCAP];
     const int tiles = P.tiles_x * P.tiles_y;
@@ -300,6 +333,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
     const uint8_t* colp = img - P.pitch + (x0 - 3);
     const uint32_t cl = (uint32_t)min(lane, W + 2 - (x0 - 3));
     auto load_row = [&](int row) { return (int)colp[(uint32_t)((row + 1) * P.pitch) + cl]; };
+    // the mask byte of image row `row` (0 <= row < H) at this lane's column, held inside the row: a
+    // halo lane outside the image is no neighbour of any pixel the tile queues
+    const uint8_t* mkp = eig_mask<MASKED>(P, b);
+    const int mpitch = eig_mpitch<MASKED>(P);
+    const uint32_t mcl = MASKED ? (uint32_t)min(max(c, 0), W - 1) : 0u;
+    auto allowed_at = [&](int row) { return !MASKED || mkp[(int64_t)row * mpitch + mcl] != 0; };
     const int g0 = max(y0 - 2, 0), g1 = min(y0 + E3_TH + 1, H - 1);   // gradient / box rows
     const int e0 = max(y0 - 1, 0);                                     // first eigen row
     const int o0 = max(y0, 1), o1 = min(y0 + E3_TH, H - 1);            // NMS rows [o0, o1)
@@ -335,6 +374,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
     // bounds, the bounds and box sums of row r-1, and the queue of possible maxima
     int loB = 0, hiB = 0, nA3 = 0, nB2 = 0, nA3H = 0, nB2H = 0;
     int TB = 0, dB = 0, sB = 0;
+    bool alB = true;                                     // masked: the pixel of row r-1 is allowed
     int nq = 0;
     uint64_t ovf = 0;                                    // own rows (bit rn - y0) the queue had no room for
     // one batch of up to 64 pixels, one per lane, from their box sums: the exact value, the
@@ -411,15 +451,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
         const int rn = r - 1;
         if constexpr (EXACT) {
             const float v = e3_exact(T, dd, sxy, sc);
+            const bool al = allowed_at(r);
             if (own && r >= y0 && r < m1) {
                 const uint32_t k = fkey(v);
-                kmax = k > kmax ? k : kmax;
+                if (al) kmax = k > kmax ? k : kmax;
                 if (P.eig_out) P.eig_out[(int64_t)b * W * H + (int64_t)r * W + c] = v;
             }
             const float mV2 = dpp_max_lr(v);
             if (ST || (rn >= o0 && rn < o1)) {
                 const float mV = fmaxf(mV2, v);
-                const bool cand = nms_col && out && eB > 0.f && eB >= fmaxf(fmaxf(mA3, mV), mB2);
+                const bool cand = nms_col && out && alB && eB > 0.f && eB >= fmaxf(fmaxf(mA3, mV), mB2);
                 const uint64_t m = __ballot(cand);
                 if (m) {
                     if (cand) kbuf[nbuf + lane_prefix(m)] = ((uint64_t)fkey(eB) << 32) | (uint32_t)(rn * W + c);
@@ -430,6 +471,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
             mA3 = fmaxf(mB2, eB);
             mB2 = mV2;
             eB = v;
+            alB = al;
         } else {
             int lo, hi;
             e3_interval(T, dd, sxy, scf, epk, lo, hi);
@@ -1513,7 +1555,7 @@ extern "C" int vo_set_gftt_select(int mode)
 // reference configuration), the tiled k_eignms otherwise (or with VO_EIG_GENERIC=1).  k_eig3
 // decides the NMS on f32 intervals and evaluates the double expression for the possible maxima
 // only; with the eigen map asked for, no key list, or VO_EIG_EXACT=1 it evaluates every pixel.
-static void launch_eig(EigParams E, hipStream_t st)
+static void launch_eig(EigParamsM E, hipStream_t st)
 {
     static const int generic = vo_env_int("VO_EIG_GENERIC", 0);
     static const int exact = vo_env_int("VO_EIG_EXACT", 0);
@@ -1521,22 +1563,31 @@ static void launch_eig(EigParams E, hipStream_t st)
         E.tiles_x = (E.W + E3_OUT - 1) / E3_OUT;
         E.tiles_y = (E.H + E3_TH - 1) / E3_TH;
         const int total = E.B * E.tiles_x * E.tiles_y;
-        if (E.eig_out || !E.keys || exact) hipLaunchKernelGGL(k_eig3<true>, dim3(((total + 7) / 8) * 8), dim3(64), 0, st, E);
-        else hipLaunchKernelGGL(k_eig3<false>, dim3(((total + 7) / 8) * 8), dim3(64), 0, st, E);
+        const dim3 grid(((total + 7) / 8) * 8);
+        const bool ex = E.eig_out || !E.keys || exact;
+        if (E.mask) {
+            hipLaunchKernelGGL((k_eig3<true, true>), grid, dim3(64), 0, st, E);      // every pixel evaluated
+        } else if (ex) {
+            hipLaunchKernelGGL(k_eig3<true>, grid, dim3(64), 0, st, (EigParams)E);
+        } else {
+            hipLaunchKernelGGL(k_eig3<false>, grid, dim3(64), 0, st, (EigParams)E);
+        }
         return;
     }
     const int total = E.B * E.tiles_x * E.tiles_y;
-    hipLaunchKernelGGL(k_eignms, dim3(((total + 7) / 8) * 8), dim3(256), 0, st, E);
+    if (E.mask) hipLaunchKernelGGL(k_eignms<true>, dim3(((total + 7) / 8) * 8), dim3(256), 0, st, E);
+    else hipLaunchKernelGGL(k_eignms<false>, dim3(((total + 7) / 8) * 8), dim3(256), 0, st, (EigParams)E);
 }
 
 // what both eigen passes share: level 0 of pyramid `cur`, the detector's options and the tiling;
 // the caller sets the outputs (keys / nkeys / ccap, chain_status, eig_out)
-static void fill_eig(EigParams& E, const vo_dims* d, const vo_opts* o, const vo_state* s, int cur)
+static void fill_eig(EigParamsM& E, const vo_dims* d, const vo_opts* o, const vo_state* s, int cur)
 {
     E.pyr = s->pyr[cur]; E.pstride = d->pyr_stride; E.W = d->W; E.H = d->H; E.pitch = d->lvl_pitch[0];
     E.off = d->lvl_off[0]; E.bs = o->feature_block_size; E.harris = o->feature_use_harris; E.harris_k = o->harris_k;
     E.eig_max = s->eig_max;
     E.B = d->B; E.tiles_x = (d->W + EIG_TW - 1) / EIG_TW; E.tiles_y = (d->H + EIG_TH - 1) / EIG_TH;
+    E.mask = nullptr; E.mstride = 0; E.mpitch = 0;
 }
 
 extern "C" int vo_gftt_eigmap(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream)
@@ -1545,7 +1596,7 @@ extern "C" int vo_gftt_eigmap(const vo_dims* d, const vo_opts* o, const vo_state
     if (o->feature_block_size < 1 || o->feature_block_size > EIG_MAXBS) return VO_EARG;
     hipStream_t st = VO_STREAM(stream);
     if (hipMemsetAsync(s->eig_max, 0, sizeof(uint32_t) * d->B, st) != hipSuccess) return VO_EHIP;
-    EigParams E;
+    EigParamsM E;
     fill_eig(E, d, o, s, cur);
     E.keys = nullptr; E.nkeys = nullptr; E.ccap = 0;
     E.chain_status = nullptr;
@@ -1561,7 +1612,7 @@ extern "C" int vo_gftt_keys(const vo_dims* d, const vo_opts* o, const vo_state* 
     hipStream_t st = VO_STREAM(stream);
     if (hipMemsetAsync(s->eig_max, 0, sizeof(uint32_t) * d->B, st) != hipSuccess) return VO_EHIP;
     if (hipMemsetAsync(s->gf_n, 0, sizeof(int32_t) * d->B, st) != hipSuccess) return VO_EHIP;
-    EigParams E;
+    EigParamsM E;
     fill_eig(E, d, o, s, cur);
     E.keys = s->gf_keys; E.nkeys = s->gf_n; E.ccap = d->ccap;
     E.chain_status = s->status;
@@ -1572,16 +1623,24 @@ extern "C" int vo_gftt_keys(const vo_dims* d, const vo_opts* o, const vo_state* 
 
 extern "C" int vo_gftt(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, vo_stream_t stream)
 {
+    return vo_gftt_masked(d, o, s, cur, nullptr, 0, 0, stream);
+}
+
+extern "C" int vo_gftt_masked(const vo_dims* d, const vo_opts* o, const vo_state* s, int cur, const uint8_t* mask,
+                              int64_t mask_stride, int32_t mask_pitch, vo_stream_t stream)
+{
     if (!d || !o || !s || cur < 0 || cur > 1) return VO_EARG;
     if (o->feature_block_size < 1 || o->feature_block_size > EIG_MAXBS) return VO_EARG;
+    if (mask && (mask_pitch < d->W || mask_stride < 0)) return VO_EARG;
     hipStream_t st = VO_STREAM(stream);
     if (hipMemsetAsync(s->eig_max, 0, sizeof(uint32_t) * d->B, st) != hipSuccess) return VO_EHIP;
     if (hipMemsetAsync(s->gf_n, 0, sizeof(int32_t) * d->B, st) != hipSuccess) return VO_EHIP;
-    EigParams E;
+    EigParamsM E;
     fill_eig(E, d, o, s, cur);
     E.keys = s->gf_keys; E.nkeys = s->gf_n; E.ccap = d->ccap;
     E.chain_status = s->status;
     E.eig_out = nullptr;
+    if (mask) { E.mask = mask; E.mstride = mask_stride; E.mpitch = mask_pitch; }
     launch_eig(E, st);
     {
         // the split selection (k_gsel_*) where it applies: a minDistance grid of cells cvRound(md)

@@ -91,17 +91,28 @@ def _gray(img):
 # ---------------------------------------------------------------- GFTT (:256)
 def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, mask=None, blockSize=3,
                         useHarrisDetector=False, k=0.04):
-    if mask is not None:
-        raise NotImplementedError("mask is not used by the reference (:256 passes None)")
+    """cv2.goodFeaturesToTrack.  ``mask``: None, or a uint8 array of the image's shape whose non-zero
+    pixels are the allowed ones (any non-zero value counts; vo_gftt_masked): the quality
+    level scales the maximum over the allowed pixels, only allowed pixels become corners, and the
+    3x3 local-maximum test still sees every neighbour.  A mask with no allowed pixel gives None."""
     img = _gray(image)
     H, W = img.shape
+    d_mask = None
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype != np.uint8 or m.shape != img.shape:
+            raise error("mask must be uint8 (CV_8UC1) and of the image's size")
+        d_mask = torch.from_numpy(np.ascontiguousarray(m)).to("cuda")
     eng = _engine(W, H, feature_max_corners=int(maxCorners), feature_quality_level=float(qualityLevel),
                   feature_min_dist=float(minDistance), feature_block_size=int(blockSize),
                   feature_use_harris=bool(useHarrisDetector))
     eng.opts.harris_k = float(k)
     eng.t["status"].zero_()
     eng.build_pyramid(img, 0)
-    L.check(eng.lib.vo_gftt(eng._pd, eng._po, eng._ps, 0, _stream()), "vo_gftt")
+    if d_mask is None:
+        L.check(eng.lib.vo_gftt(eng._pd, eng._po, eng._ps, 0, _stream()), "vo_gftt")
+    else:
+        L.check(eng.lib.vo_gftt_masked(eng._pd, eng._po, eng._ps, 0, _p(d_mask), W * H, W, _stream()), "vo_gftt_masked")
     st = int(eng.t["status"][0])
     if st != 0:
         raise error(L.STATUS_NAMES.get(st, str(st)))
