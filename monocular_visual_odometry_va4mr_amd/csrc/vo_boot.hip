@@ -865,7 +865,7 @@ static void fill_ess(EssArgs& A, const vo_opts* o, const float* p0, const float*
 
 static void launch_essential(const EssArgs& A, int B, hipStream_t st)
 {
-    const int n_cu = device_cus() > 0 ? device_cus() : 256;          // of the current device
+    const int n_cu = launch_cus();
     if (B > n_cu) hipLaunchKernelGGL(k_essential<2>, dim3(B), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(k_essential<1>, dim3(B), dim3(256), 0, st, A);
 }
@@ -924,7 +924,7 @@ extern "C" int vo_bootstrap(const vo_dims* d, const vo_opts* o, const vo_state* 
     Rg.E = Ebuf; Rg.p0 = s->c_first; Rg.p1 = s->c_kp; Rg.counts = s->nC; Rg.cap = d->pcap;
     Rg.R = Rbuf; Rg.t = tbuf; Rg.mask = nullptr; Rg.n_good = s->pnp_ninl; Rg.chain_status = s->status;
     Rg.sign_fix = 1;
-    if (d->B >= (device_cus() > 0 ? device_cus() : 256)) {
+    if (d->B >= launch_cus()) {
         hipLaunchKernelGGL(k_recover_pose, dim3(d->B), dim3(256), 0, st, Rg);
     } else {
         hipLaunchKernelGGL(k_recover_count, dim3(d->B, RP_SPLIT), dim3(256), 0, st, Rg, gcount);

@@ -242,6 +242,14 @@ static inline int device_cus()
     return n;
 }
 
+// host: the compute-unit count that the launch shapes compare a batch against (256 where the
+// device does not tell)
+static inline int launch_cus()
+{
+    const int n = device_cus();
+    return n > 0 ? n : 256;
+}
+
 // feature_tracking's filtering (VisualOdometryPipeLine.py:283-290) for chain blockIdx.x: the
 // tracked landmarks and candidates with status 1, in order (ordered compaction from the tracking
 // scratch trk_pts / trk_st)
