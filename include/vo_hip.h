@@ -138,9 +138,10 @@ int vo_device_cus(void);                          /* compute units of the curren
  * unconstrained forms below).  n > 0 makes those decisions assume n CUs (test hook: every form
  * on a small batch); n = 0 restores the device's own count.  Results never depend on it. */
 int vo_set_launch_cus(int n);
-/* Form of the GFTT corner selection inside vo_gftt (goodFeaturesToTrack's sort + minDistance
- * walk, VisualOdometryPipeLine.py:256): 0 = automatic (the split one-wave kernels k_gsel_* where
- * the configuration allows them, else k_gftt_select), 1 = always the one-block k_gftt_select,
+/* Form of the GFTT corner selection inside vo_gftt (csrc/vo_select.hip: goodFeaturesToTrack's sort
+ * + minDistance walk, VisualOdometryPipeLine.py:256): 0 = automatic (above 64 chains the split
+ * one-wave kernels k_gsel_* where the configuration allows them, else k_gftt_select), 1 = always
+ * the one-block k_gftt_select,
  * 2 = the split form where it applies.  Test / A-B hook; the corner lists are identical. */
 int vo_set_gftt_select(int mode);
 /* A HIP stream of the current device whose kernels may run on every compute unit except

@@ -218,6 +218,10 @@ VO_DEV uint32_t rng_next(uint64_t& s)
 static inline bool hip_ok() { return hipGetLastError() == hipSuccess; }
 static inline int hip_rc() { return hip_ok() ? VO_OK : VO_EHIP; }
 
+// host: goodFeaturesToTrack's selection (vo_select.hip) over the key list the eigen pass of
+// vo_gftt.hip left in s->gf_keys / s->gf_n: the corners into s->corners / s->nCorners
+int vo_gftt_select(const vo_dims* d, const vo_opts* o, const vo_state* s, hipStream_t stream);
+
 // host: an integer tuning knob from the environment (tools/README.md lists them); the call sites
 // keep the value in a static const, so it is read once per process
 static inline int vo_env_int(const char* name, int dflt)

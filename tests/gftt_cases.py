@@ -6,7 +6,7 @@ oracle.gftt; walk_model exists to show on the CPU that an input can tell a right
 wrong one (test_gftt_cases_ref.py), and test_gpu_gftt_select_edges.py runs the same cases through
 both selection forms.
 
-The constants the cases aim at (vo_gftt.hip): k_gftt_select takes its keys in pages of PAGE = 4096,
+The constants the cases aim at (vo_select.hip): k_gftt_select takes its keys in pages of PAGE = 4096,
 decides inside a page on exact conflict lists and consults its cell grid only for corners accepted
 on earlier pages; the grid's cells are cvRound(minDistance) pixels wide; the split form takes cells
 up to 255 pixels wide whose u64 grid fits the eigen-map scratch (cells * 8 + 4 <= 4 * W * H).
@@ -16,6 +16,13 @@ import functools
 import numpy as np
 
 PAGE = 4096
+# where k_gftt_select keeps its cell grid (vo_select.hip): in LDS up to GRID_LDS_CELLS cells that fit
+# the LDS budget beside the page and the accepted corners (at most ACC_MAX of them there), else in
+# the chain's W * H u32 of scratch behind the conflict lists, else in that scratch with no room for
+# the lists (the wave-serial walk)
+GRID_LDS_CELLS = 22528
+ACC_MAX = 8192
+LDS_BUDGET = 150 * 1024
 
 
 # ---------------------------------------------------------------------- the host model
@@ -235,6 +242,11 @@ def cases():
         for md in mds:
             c[f"crop_{W}x{H}_md{md}"] = (crop(W, H), GRID_QUALITY, md, MC)
             c[f"noise_{W}x{H}_md{md}"] = (noise(W, H), GRID_QUALITY, md, MC)
+    # a grid that fits neither LDS nor the scratch behind the conflict lists (k_gftt_select's
+    # wave-serial walk over the L2 grid): 6,000 cells of 2 pixels, where the split form applies, and
+    # 8,777 cells of 1 pixel, where it does not
+    c["noise_200x120_md2.5"] = (noise(200, 120), GRID_QUALITY, 2.5, MC)
+    c["binary_131x67_md1.49"] = (binary(131, 67), GRID_QUALITY, 1.49, MC)
     c["noise_64x64_md1.6_mc1"] = (noise(64, 64), GRID_QUALITY, 1.6, 1)
     c["noise_64x64_md1.6_mc0"] = (noise(64, 64), GRID_QUALITY, 1.6, 0)
     c["noise_64x64_md1.6_mc-1"] = (noise(64, 64), GRID_QUALITY, 1.6, -1)

@@ -156,6 +156,37 @@ def test_grid_edge_cases_reach_their_regimes():
             assert 1 <= len(GC.expect(name)) < n, name
 
 
+def _grid_placement(W, H, md, mcap=GC.MC):
+    """where k_gftt_select keeps its cell grid: the host's arithmetic (vo_select.hip), restated"""
+    if md < 1:
+        return "no grid"
+    cs = int(np.rint(md))
+    cells = -(-W // cs) * -(-H // cs)
+    acc_lds = min(mcap, GC.ACC_MAX)
+    if cells <= GC.GRID_LDS_CELLS and 16 * PAGE + 6 * acc_lds + 8 * cells <= GC.LDS_BUDGET:
+        return "lds"
+    if 8 * PAGE + 2 * cells <= W * H:
+        return "l2 behind the conflict lists"
+    return "l2 alone"
+
+
+def test_grid_placements_are_all_reached():
+    """every placement of k_gftt_select's grid has a case: the two cases built for the wave-serial
+    walk over the L2 grid land there, and older cases land on the two parallel placements"""
+    c = GC.cases()
+    where = {name: _grid_placement(img.shape[1], img.shape[0], md) for name, (img, q, md, mc) in c.items()}
+    serial = {"noise_200x120_md2.5", "binary_131x67_md1.49"}
+    assert {n for n, w in where.items() if w == "l2 alone"} >= serial
+    for name in serial:
+        img, q, md, mc = c[name]
+        n = len(GC.passing_keys(img, q)[0])
+        assert mc == GC.MC and 64 < len(GC.expect(name)) < n < PAGE, name   # several rounds, rejections
+    assert GC.split_applies(200, 120, 2.5, GC.MC) and not GC.split_applies(131, 67, 1.49, GC.MC)
+    older = {n: w for n, w in where.items() if n not in serial}
+    assert "lds" in older.values() and "l2 behind the conflict lists" in older.values()
+    assert where["three_in_cell_md40"] == "lds" and where["checker4_md2"] == "l2 behind the conflict lists"
+
+
 def test_max_corners_limits():
     c = GC.cases()
     assert len(GC.expect("noise_64x64_md1.6_mc1")) == 1

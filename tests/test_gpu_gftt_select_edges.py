@@ -107,6 +107,27 @@ def test_four_mixed_chains_both_forms(sel_mode):
     assert all(len(v) == 1 for v in passing.values()), f"passing-key counts {passing}"
 
 
+def test_more_than_128_chains_one_block_form(sel_mode):
+    """130 chains in one launch of the one-block form: above 128 chains k_gftt_select runs with 512
+    threads per chain instead of 1024.  Chain b holds frame b % 4 of the mixed launch above;
+    three_in_cell_md40's 5,100 keys take the radix select and a second page."""
+    from oracle import _olib as O
+    W, H, B = 320, 240, 130
+    q, md, mc = GC.THREE_QUALITY, 40.0, GC.MC
+    frames = [GC.cases()["three_in_cell_md40"][0], GC.checker4(), np.full((H, W), 77, np.uint8), GC.crop(W, H)]
+    refs = [GC.expect("three_in_cell_md40"), GC.expect("checker4_md40"), O.gftt(frames[2], mc, q, md),
+            O.gftt(frames[3], mc, q, md)]
+    eng = _engine(W, H, B=B)
+    sel_mode(1)
+    out, gf_n = _select(eng, np.stack([frames[b % 4] for b in range(B)]), q, md, mc)
+    del _ENGINES[W, H, B]                 # 0.2 GB, used by this test alone
+    for b in range(B):
+        got, n = out[b]
+        assert n == len(refs[b % 4]) and np.array_equal(got, refs[b % 4]), f"chain {b}: {n} vs {len(refs[b % 4])}"
+        assert gf_n[b] == gf_n[b % 4], f"chain {b}: {gf_n[b]} passing keys, chain {b % 4} {gf_n[b % 4]}"
+    assert gf_n[0] == 5100
+
+
 @pytest.mark.parametrize("name,md", [("three_in_cell_md40", 40.0), ("checker4_md2", 2)])
 def test_cv2compat_unlimited_corners(name, md):
     """cv2compat.goodFeaturesToTrack with maxCorners = 0 (the one-block form at the engine's capacity)"""

@@ -4,7 +4,7 @@
 #   bash tools/gpu.sh bench  <tag> [bench args]       one bench line -> gpurun_out/<tag>.json
 #   bash tools/gpu.sh ab     <tag> <reps> <A env> <B env> [bench args]
 #                                                     headline A/B alternating two env settings,
-#                                                     e.g. VO_SEL_SPLIT=1 VO_SEL_SPLIT=0 (AB_ARGS replaces
+#                                                     e.g. VO_ADD_LEAN=1 VO_ADD_LEAN=0 (AB_ARGS replaces
 #                                                     the default headline-only flags)
 #   bash tools/gpu.sh abargs <tag> <reps> "<flags A>" "<flags B>"   the same over two bench flag sets
 #   bash tools/gpu.sh timeline <tag> [bench args]     per-queue kernel timeline of the headline

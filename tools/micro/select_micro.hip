@@ -1,6 +1,6 @@
 // Phase timing of k_gftt_select for one chain with real candidate keys (KITTI frame):
 // build with -DVO_SELECT_PROF; keys from tools/micro/keys*.bin (written by a host script).
-#include "../../monocular_visual_odometry_va4mr_amd/csrc/vo_gftt.hip"
+#include "../../monocular_visual_odometry_va4mr_amd/csrc/vo_select.hip"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase times of k_gftt_select (block 0 of the launch) on the headline workload: B KITTI
+"""Phase times of k_gftt_select (csrc/vo_select.hip; block 0 of the launch) on the headline workload: B KITTI
 chains, every stage on one stream.  Needs the diagnostics build
 (make -C monocular_visual_odometry_va4mr_amd/csrc ../_build/libvo_hip_selprof.so).
 usage: python tools/sel_prof.py [B] [steps] [preset]"""
