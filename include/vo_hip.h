@@ -321,6 +321,54 @@ int vo_filter_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_st
                                  int32_t refine_iters, double refine_ftol, double* refine_info,
                                  vo_stream_t stream);
 
+/* The optional reprojection-error gate on new landmarks (engine option tri_max_reproj_error; the
+ * project's own definition, DESIGN 5g and the NumPy restatement tests/test_tri_gate_ref.py,
+ * reproduced bit for bit).  No reference counterpart: triangulate_landmarks (:107-206) tests a
+ * new point against the bearing angle (:117-147) and the two depths (:149-168) only.
+ *   A candidate that reached cv2.triangulatePoints (:188) and passed the depth gate becomes a
+ * landmark iff its float32 point X (the one the depth gate saw), promoted to double, reprojects
+ * within max_reproj_error pixels of both observations it was made from: for the past view
+ * (P_past, c_first) and the current view (P_cur, c_kp), with the very 3x4 matrices given to
+ * cv2.triangulatePoints and one fp64 rounding per operation (no fused multiply-add),
+ *     p_k = ((P_k0 X + P_k1 Y) + P_k2 Z) + P_k3   (k = 0, 1, 2)
+ *     du = p_0 / p_2 - x,  dv = p_1 / p_2 - y,  e = du du + dv dv
+ * and the view passes iff p_2 > 0 and e <= max_reproj_error^2 (squared once on the host, in
+ * double; a NaN fails).  A candidate with a failing view is removed: neither appended to the
+ * landmarks nor kept among the candidates.  The frame gate (:175-178), check_baseline, the depth
+ * gate and its "keep", and the order of the appended landmarks and of the kept candidates stay the
+ * reference's.  vo_bootstrap's triangulation (:319) is never gated.
+ *   info: [B][4] int32 or NULL.  A chain that triangulates writes: candidates that reached
+ * cv2.triangulatePoints, those of them the depth gate kept as candidates, those this gate dropped,
+ * those appended as landmarks (counted even where the capacity could not hold them and the chain
+ * ends with VO_ST_CAPACITY).  A chain with status 0 that does not triangulate (:366) writes four
+ * zeros; a chain whose status is set keeps its row. */
+typedef struct vo_tri_opts {
+    double max_reproj_error;      /* pixels; finite and > 0                               */
+    int32_t* info;                /* [B][4] counters (device memory) or NULL              */
+} vo_tri_opts;
+
+/* vo_triangulate with that gate, in both of its forms (one launch; gate / solve / append).
+ * tri == NULL is vo_triangulate itself, with the same launches.  max_reproj_error that is not
+ * finite and > 0: VO_EARG with nothing launched (so for the three calls below). */
+int vo_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int force,
+                         const vo_tri_opts* tri, vo_stream_t stream);
+
+/* vo_pnp_triangulate_ex and vo_filter_pnp_triangulate_ex with the gate in their triangulation,
+ * with or without the pose refinement (refine_iters = 0: off), in kernels of their own.  tri ==
+ * NULL is the _ex call, with the same launches. */
+int vo_pnp_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                             double refine_ftol, double* refine_info, const vo_tri_opts* tri,
+                             vo_stream_t stream);
+int vo_filter_pnp_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s,
+                                    int32_t refine_iters, double refine_ftol, double* refine_info,
+                                    const vo_tri_opts* tri, vo_stream_t stream);
+
+/* vo_pnp_ex as the first half of the unfused gated step: it checks tri like the calls above, then
+ * is vo_pnp_ex (PnP does not triangulate, so nothing else of tri is used; the vo_triangulate_gated
+ * call that follows applies it). */
+int vo_pnp_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                 double refine_ftol, double* refine_info, const vo_tri_opts* tri, vo_stream_t stream);
+
 /* Sub-pixel refinement of corner positions in the form of cv2.cornerSubPix; the project's own
  * definition (the NumPy restatement tests/test_subpix_ref.py), reproduced bit for bit.
  * Plain device images: image b is H rows of W u8 pixels at img + b * img_stride, `pitch` bytes
@@ -345,6 +393,13 @@ int vo_corner_subpix(int B, const uint8_t* img, int64_t img_stride, int32_t pitc
  * one pair per point), x1,x2 [n][2] -> out [n][4] float32. */
 int vo_triangulate_points(int n, const double* P1, const double* P2, const float* x1,
                           const float* x2, float* out4, vo_stream_t stream);
+
+/* vo_triangulate_points, and the quantity the reprojection gate (vo_tri_opts) compares: err2
+ * [n][2] double, the e of the float32 point out4[:3] / out4[3] (float32 divisions, as :189)
+ * against (P1, x1) and (P2, x2), evaluated exactly as defined there; +inf where p_2 is not > 0.
+ * out4 is vo_triangulate_points' bit for bit.  No reference counterpart. */
+int vo_triangulate_points_err(int n, const double* P1, const double* P2, const float* x1,
+                              const float* x2, float* out4, double* err2, vo_stream_t stream);
 
 /* cv2.Rodrigues (:354): n vectors [n][3] -> matrices [n][9], or the inverse. */
 int vo_rodrigues(int n, int to_matrix, const double* in, double* out, vo_stream_t stream);

@@ -26,9 +26,11 @@ reference's: ``sift_nfeatures``, and ``lk_fb_threshold`` (pixels; absent or None
 drops every tracked point that LK from the new frame back to the old one does not return to
 within that distance of where it started (vo_track_fb), ``pnp_refine_iters``
 (absent, None or 0 = off; ``pnp_refine_ftol``), which refines every PnP pose by Levenberg-Marquardt
-on the inliers' reprojection error, and ``feature_subpix_win`` (half-window; absent or
+on the inliers' reprojection error, ``feature_subpix_win`` (half-window; absent or
 None = off; ``feature_subpix_iters``, ``feature_subpix_eps``, ``feature_subpix_zero_zone``), which
-refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix).
+refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix), and
+``tri_max_reproj_error`` (pixels; absent or None = off), which drops a triangulated candidate whose
+new landmark reprojects further than that from either of its two observations.
 """
 from __future__ import annotations
 

@@ -85,6 +85,11 @@ class VoState(C.Structure):
     _fields_ = [(n, vp) for n in _STATE_FIELDS]
 
 
+class VoTriOpts(C.Structure):
+    """vo_tri_opts: the reprojection-error gate on new landmarks (info: [B][4] int32 or None)."""
+    _fields_ = [("max_reproj_error", f64), ("info", vp)]
+
+
 VO_SIFT_MAX_OCT = 16
 
 
@@ -128,6 +133,7 @@ def _declare(L):
     D = C.POINTER(VoDims)
     O = C.POINTER(VoOpts)
     S = C.POINTER(VoState)
+    TG = C.POINTER(VoTriOpts)
     sig = {
         "vo_version": ([], C.c_char_p),
         "vo_device_arch": ([C.c_char_p, C.c_int], C.c_int),
@@ -162,7 +168,12 @@ def _declare(L):
         "vo_pnp_ex": ([D, O, S, i32, f64, P, P], C.c_int),
         "vo_pnp_triangulate_ex": ([D, O, S, i32, f64, P, P], C.c_int),
         "vo_filter_pnp_triangulate_ex": ([D, O, S, i32, f64, P, P], C.c_int),
+        "vo_triangulate_gated": ([D, O, S, C.c_int, TG, P], C.c_int),
+        "vo_pnp_gated": ([D, O, S, i32, f64, P, TG, P], C.c_int),
+        "vo_pnp_triangulate_gated": ([D, O, S, i32, f64, P, TG, P], C.c_int),
+        "vo_filter_pnp_triangulate_gated": ([D, O, S, i32, f64, P, TG, P], C.c_int),
         "vo_triangulate_points": ([C.c_int, P, P, P, P, P, P], C.c_int),
+        "vo_triangulate_points_err": ([C.c_int, P, P, P, P, P, P, P], C.c_int),
         "vo_rodrigues": ([C.c_int, C.c_int, P, P, P], C.c_int),
     }
     SB = C.POINTER(VoSiftBuf)

@@ -1266,6 +1266,35 @@ struct TriShared {
     int fail, m;
 };
 
+// The optional reprojection-error gate on new landmarks (vo_tri_opts; no reference counterpart,
+// DESIGN 5g).  Only the GATED instantiations below read it: the kernels that run with the gate
+// off take no TriGate and compile to what they were without it.
+struct TriGate {
+    double thr2;           // max_reproj_error^2, squared once on the host
+    int32_t* info;         // [B][4] reached / kept by the depth gate / dropped / appended, or nullptr
+};
+
+// Squared pixel error of the float32 point X in the view (P, (x, y)), every term promoted to
+// double, one rounding per operation in the order of tests/test_tri_gate_ref.reproj_err2 (the
+// build's -ffp-contract=off keeps the products and sums apart); *p2 = the projective depth
+VO_DEV double reproj_err2(const double* P, const float* X, float x, float y, double* p2)
+{
+    const double Xd = (double)X[0], Yd = (double)X[1], Zd = (double)X[2];
+    double p[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = ((P[4 * k] * Xd + P[4 * k + 1] * Yd) + P[4 * k + 2] * Zd) + P[4 * k + 3];
+    const double du = p[0] / p[2] - (double)x, dv = p[1] / p[2] - (double)y;
+    *p2 = p[2];
+    return du * du + dv * dv;
+}
+// the view passes iff the point is in front of it and within the gate; NaN fails either test
+VO_DEV bool reproj_pass(const double* P, const float* X, float x, float y, double thr2)
+{
+    double p2;
+    const double e = reproj_err2(P, X, x, y, &p2);
+    return p2 > 0.0 && e <= thr2;
+}
+
 // false: the chain does not triangulate this step (status set, or :366's nC <= 1)
 VO_DEV bool tri_setup(const TriArgs& A, TriShared& sh)
 {
@@ -1347,8 +1376,10 @@ VO_DEV void tri_gate(const TriArgs& A, TriShared& sh)
     __syncthreads();
 }
 
-// pass 2 over list entries j0, j0 + stride, ... (m entries)
-VO_DEV void tri_solve(const TriArgs& A, const TriShared& sh, int m, int j0, int stride)
+// pass 2 over list entries j0, j0 + stride, ... (m entries).  GATED: a candidate that passed the
+// depth gate must also reproject onto its two observations within G->thr2, else tacc = 2 (dropped)
+template <bool GATED>
+VO_DEV void tri_solve(const TriArgs& A, const TriShared& sh, int m, int j0, int stride, const TriGate* G = nullptr)
 {
     const int b = blockIdx.x;
     const vo_dims& d = A.d;
@@ -1382,14 +1413,23 @@ VO_DEV void tri_solve(const TriArgs& A, const TriShared& sh, int m, int j0, int 
         const double zc = depth_of(sh.Rcwc, sh.tcwc, nF, Xo);
         const double zp = depth_of(Rpw, tpw, tau, Xo);
         if (zc > A.min_d && zp > A.min_d && zc < A.max_d && zp < A.max_d) {
+            if constexpr (GATED) {
+                if (!(reproj_pass(Pp, Xo, f0, f1, G->thr2) && reproj_pass(sh.Pc, Xo, k0, k1, G->thr2))) {
+                    tacc[i] = 2;                                        // neither landmark nor candidate
+                    continue;
+                }
+            }
             tacc[i] = 1;
             tX[3 * i] = Xo[0]; tX[3 * i + 1] = Xo[1]; tX[3 * i + 2] = Xo[2];
         }                                                               // else retained (quirk Q5)
     }
 }
 
-// pass 3: ordered append of the accepted candidates to the landmarks, in-place compaction of the rest
-VO_DEV void tri_append(const TriArgs& A, TriShared& sh)
+// pass 3: ordered append of the accepted candidates to the landmarks, in-place compaction of the
+// rest.  GATED: a dropped candidate (tacc = 2) advances neither the landmark scan nor the kept
+// count, and thread 0 writes the chain's four counters (m = sh.m, the list length of pass 1).
+template <bool GATED>
+VO_DEV void tri_append(const TriArgs& A, TriShared& sh, const TriGate* G = nullptr)
 {
     __shared__ int lds[16];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -1405,20 +1445,30 @@ VO_DEV void tri_append(const TriArgs& A, TriShared& sh)
     const int32_t* tacc = s.iwork + (int64_t)b * d.iwork_stride + kmax;
     const float* tX = (const float*)(s.work + (int64_t)b * d.work_stride);
     int nL = s.nL[b];
+    const int nL0 = nL;
     int kept = 0;
     for (int base = 0; base < nC; base += blockDim.x) {
         const int i = base + tid;
         const int nvalid = nC - base < (int)blockDim.x ? nC - base : (int)blockDim.x;
         const bool valid = i < nC;
-        bool accept = false;
+        bool accept = false, keep = false;
         float k0 = 0, k1 = 0, f0 = 0, f1 = 0;
         int tau = 0;
         if (valid) {
             k0 = ck[2 * i]; k1 = ck[2 * i + 1]; f0 = cf[2 * i]; f1 = cf[2 * i + 1]; tau = ct[i];
-            accept = tacc[i] != 0;
+            if constexpr (GATED) {
+                const int a = tacc[i];
+                accept = a == 1;
+                keep = a == 0;
+            } else {
+                accept = tacc[i] != 0;
+            }
         }
         int tacc_n;
         const int pre = block_scan_flag(accept, lds, &tacc_n);          // every thread before tid is valid
+        int keep_n = nvalid - tacc_n, kpre = tid - pre;
+        if constexpr (GATED) kpre = block_scan_flag(keep, lds, &keep_n);
+        else keep = valid && !accept;
         if (accept) {
             const int pa = nL + pre;
             if (pa < d.ncap) {
@@ -1427,34 +1477,61 @@ VO_DEV void tri_append(const TriArgs& A, TriShared& sh)
             } else {
                 sh.fail = 1;
             }
-        } else if (valid) {
-            const int pr = kept + (tid - pre);
+        } else if (keep) {
+            const int pr = kept + kpre;
             ck[2 * pr] = k0; ck[2 * pr + 1] = k1; cf[2 * pr] = f0; cf[2 * pr + 1] = f1; ct[pr] = tau;
         }
         nL += tacc_n;
-        kept += nvalid - tacc_n;
+        kept += keep_n;
         __syncthreads();
     }
     if (tid == 0) {
         s.nL[b] = nL < d.ncap ? nL : d.ncap;
         s.nC[b] = kept;
         if (sh.fail) s.status[b] = VO_ST_CAPACITY;
+        if constexpr (GATED) {
+            if (G->info) {
+                // of the m candidates that reached cv2.triangulatePoints: nC - m never did and are all
+                // kept, so the depth gate kept the rest of `kept`; what is neither kept nor appended
+                // was dropped.  Appended counts the accepted ones even past the capacity.
+                const int m = sh.m, app = nL - nL0, dkept = kept - (nC - m);
+                int32_t* o = G->info + 4 * (int64_t)b;
+                o[0] = m; o[1] = dkept; o[2] = m - dkept - app; o[3] = app;
+            }
+        }
     }
 }
 
-VO_DEV void triangulate_block(const TriArgs& A)
+// a chain with status 0 that does not triangulate this step (:366) reports four zeros; one with a
+// status set keeps its row
+VO_DEV void tri_info_idle(const TriArgs& A, const TriGate& G)
 {
-    __shared__ TriShared sh;
-    if (!tri_setup(A, sh)) return;
-    tri_gate(A, sh);
-    PNPPROF(26);
-    tri_solve(A, sh, sh.m, threadIdx.x, blockDim.x);
-    __syncthreads();
-    PNPPROF(27);
-    tri_append(A, sh);
+    if (threadIdx.x == 0 && G.info && A.s.status[blockIdx.x] == 0) {
+        int32_t* o = G.info + 4 * (int64_t)blockIdx.x;
+        o[0] = o[1] = o[2] = o[3] = 0;
+    }
 }
 
-__global__ void __launch_bounds__(256) k_triangulate(TriArgs A) { triangulate_block(A); }
+template <bool GATED>
+VO_DEV void triangulate_block(const TriArgs& A, const TriGate* G = nullptr)
+{
+    __shared__ TriShared sh;
+    if (!tri_setup(A, sh)) {
+        if constexpr (GATED) tri_info_idle(A, *G);
+        return;
+    }
+    tri_gate(A, sh);
+    PNPPROF(26);
+    tri_solve<GATED>(A, sh, sh.m, threadIdx.x, blockDim.x, G);
+    __syncthreads();
+    PNPPROF(27);
+    tri_append<GATED>(A, sh, G);
+}
+
+__global__ void __launch_bounds__(256) k_triangulate(TriArgs A) { triangulate_block<false>(A); }
+// with the reprojection gate: a kernel of its own, as every gated form below (k_triangulate is what
+// runs with the option off)
+__global__ void __launch_bounds__(256) k_triangulate_gated(TriArgs A, TriGate G) { triangulate_block<true>(A, &G); }
 
 // vo_triangulate as three launches: the gate (one block per chain, list length into iwork), the
 // triangulations over TRI_SPLIT blocks per chain, the ordered append (one block per chain).  With
@@ -1477,13 +1554,35 @@ __global__ void __launch_bounds__(256) k_tri_solve(TriArgs A)
     if (!tri_setup(A, sh)) return;
     const int kmax = A.d.ncap > A.d.pcap ? A.d.ncap : A.d.pcap;
     const int m = A.s.iwork[(int64_t)blockIdx.x * A.d.iwork_stride + 2 * kmax];
-    tri_solve(A, sh, m, blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x);
+    tri_solve<false>(A, sh, m, blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x);
 }
 __global__ void __launch_bounds__(256) k_tri_append(TriArgs A)
 {
     __shared__ TriShared sh;
     if (!tri_setup(A, sh)) return;
-    tri_append(A, sh);
+    tri_append<false>(A, sh);
+}
+// the gated split form: k_tri_gate as it is, then these two
+__global__ void __launch_bounds__(256) k_tri_solve_gated(TriArgs A, TriGate G)
+{
+    __shared__ TriShared sh;
+    if (!tri_setup(A, sh)) return;
+    const int kmax = A.d.ncap > A.d.pcap ? A.d.ncap : A.d.pcap;
+    const int m = A.s.iwork[(int64_t)blockIdx.x * A.d.iwork_stride + 2 * kmax];
+    tri_solve<true>(A, sh, m, blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x, &G);
+}
+__global__ void __launch_bounds__(256) k_tri_append_gated(TriArgs A, TriGate G)
+{
+    __shared__ TriShared sh;
+    if (!tri_setup(A, sh)) {
+        tri_info_idle(A, G);
+        return;
+    }
+    if (threadIdx.x == 0) {                 // the list length k_tri_gate left (only thread 0 reads sh.m)
+        const int kmax = A.d.ncap > A.d.pcap ? A.d.ncap : A.d.pcap;
+        sh.m = A.s.iwork[(int64_t)blockIdx.x * A.d.iwork_stride + 2 * kmax];
+    }
+    tri_append<true>(A, sh, &G);
 }
 
 // vo_pnp + vo_triangulate(force 0) as one launch (the engine's step): the triangulation of a
@@ -1504,7 +1603,7 @@ k_pnp_tri(PnPArgs A, TriArgs T)
     pnp_apply_split(T.d, T.s, A.rvec, A.tvec, A.success, A.mask, defer, pend);
     __syncthreads();
     PNPPROF(14);
-    triangulate_block(T);
+    triangulate_block<false>(T);
     PNPPROF(15);
 }
 
@@ -1528,7 +1627,33 @@ k_pnp_tri_ref(PnPArgs A, TriArgs T, RefArgs Rf)
     pnp_refine_state(A, T.d, T.s, Rf);
     __syncthreads();
     PNPPROF(14);
-    triangulate_block(T);
+    triangulate_block<false>(T);
+    PNPPROF(15);
+}
+
+// k_pnp_tri / k_pnp_tri_ref with the reprojection gate in the triangulation (REF: with the LM
+// refinement).  Kernels of their own, so that the two above stay what they are.
+template <int WPE, bool REF>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
+k_pnp_tri_gated(PnPArgs A, TriArgs T, RefArgs Rf, TriGate G)
+{
+    if (T.compact) {
+        track_compact_block(T.d, T.s);
+        __syncthreads();
+    }
+    __shared__ double defer[12];
+    __shared__ int pend;
+    if (threadIdx.x == 0) pend = 0;
+    pnp_ransac_block(A, defer, &pend);
+    __syncthreads();
+    pnp_apply_split(T.d, T.s, A.rvec, A.tvec, A.success, A.mask, defer, pend);
+    __syncthreads();
+    if constexpr (REF) {
+        pnp_refine_state(A, T.d, T.s, Rf);
+        __syncthreads();
+    }
+    PNPPROF(14);
+    triangulate_block<true>(T, &G);
     PNPPROF(15);
 }
 
@@ -1540,6 +1665,25 @@ __global__ void k_tri_points(int n, const double* P1, const double* P2, const fl
     double X4[4];
     tri_one(P1 + 12 * i, P2 + 12 * i, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], X4);
     for (int q = 0; q < 4; ++q) out[4 * i + q] = (float)X4[q];
+}
+
+// k_tri_points plus the quantity the reprojection gate compares: the float32 dehomogenised point
+// (tri_solve's Xo) against each of its two views, +inf where the projective depth is not > 0
+__global__ void __launch_bounds__(128) k_tri_points_err(int n, const double* P1, const double* P2, const float* x1, const float* x2, float* out,
+                                 double* err2)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double X4[4];
+    tri_one(P1 + 12 * i, P2 + 12 * i, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], X4);
+    for (int q = 0; q < 4; ++q) out[4 * i + q] = (float)X4[q];
+    const float w4 = (float)X4[3];
+    const float Xo[3] = {(float)X4[0] / w4, (float)X4[1] / w4, (float)X4[2] / w4};
+    double p2;
+    const double e1 = reproj_err2(P1 + 12 * i, Xo, x1[2 * i], x1[2 * i + 1], &p2);
+    err2[2 * i] = p2 > 0.0 ? e1 : (double)INFINITY;
+    const double e2 = reproj_err2(P2 + 12 * i, Xo, x2[2 * i], x2[2 * i + 1], &p2);
+    err2[2 * i + 1] = p2 > 0.0 ? e2 : (double)INFINITY;
 }
 
 __global__ void k_rodrigues(int n, int to_matrix, const double* in, double* out)
@@ -1668,12 +1812,55 @@ extern "C" int vo_triangulate(const vo_dims* d, const vo_opts* o, const vo_state
     return hip_rc();
 }
 
+// max_reproj_error finite and > 0 (NaN fails the first test)
+static inline bool tri_opts_ok(const vo_tri_opts* t)
+{
+    return t->max_reproj_error > 0.0 && t->max_reproj_error <= 1.7976931348623157e308;
+}
+
+static inline TriGate make_gate(const vo_tri_opts* t)
+{
+    TriGate G;
+    G.thr2 = t->max_reproj_error * t->max_reproj_error;
+    G.info = t->info;
+    return G;
+}
+
+extern "C" int vo_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int force,
+                                    const vo_tri_opts* tri, vo_stream_t stream)
+{
+    if (!tri) return vo_triangulate(d, o, s, force, stream);
+    if (!d || !o || !s || !tri_opts_ok(tri)) return VO_EARG;
+    TriArgs A;
+    fill_tri(A, d, o, s, force);
+    const int kmax = d->ncap > d->pcap ? d->ncap : d->pcap;
+    if (d->iwork_stride < 2LL * kmax + 1) return VO_EARG;
+    const TriGate G = make_gate(tri);
+    hipStream_t st = VO_STREAM(stream);
+    if (d->B >= launch_cus()) {
+        hipLaunchKernelGGL(k_triangulate_gated, dim3(d->B), dim3(256), 0, st, A, G);
+    } else {
+        hipLaunchKernelGGL(k_tri_gate, dim3(d->B), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(k_tri_solve_gated, dim3(d->B, TRI_SPLIT), dim3(256), 0, st, A, G);
+        hipLaunchKernelGGL(k_tri_append_gated, dim3(d->B), dim3(256), 0, st, A, G);
+    }
+    return hip_rc();
+}
+
+extern "C" int vo_pnp_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters, double refine_ftol,
+                            double* refine_info, const vo_tri_opts* tri, vo_stream_t stream)
+{
+    if (tri && !tri_opts_ok(tri)) return VO_EARG;
+    return vo_pnp_ex(d, o, s, refine_iters, refine_ftol, refine_info, stream);
+}
+
 static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s, int compact, int32_t refine_iters,
-                          double refine_ftol, double* refine_info, vo_stream_t stream)
+                          double refine_ftol, double* refine_info, const vo_tri_opts* tri, vo_stream_t stream)
 {
     if (!d || !o || !s) return VO_EARG;
     if (d->work_stride < 12LL * d->ncap + 64) return VO_EARG;
     if (!refine_args_ok(refine_iters, refine_ftol)) return VO_EARG;
+    if (tri && !tri_opts_ok(tri)) return VO_EARG;
     PnPArgs P;
     fill_pnp_engine(P, d, o, s);
     TriArgs T;
@@ -1685,6 +1872,21 @@ static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s,
     static const int force = vo_env_int("VO_PNP_TRI_WPE", 0);
     const int n_cu = launch_cus();
     const bool two = force ? force == 2 : d->B > n_cu;
+    if (tri) {
+        // the gated kernels, with or without the refinement
+        const TriGate G = make_gate(tri);
+        RefArgs Rf = {refine_iters, refine_ftol, refine_info};
+        const dim3 g(d->B), t(256);
+        hipStream_t st = VO_STREAM(stream);
+        if (refine_iters > 0) {
+            if (two) hipLaunchKernelGGL((k_pnp_tri_gated<VO_PNP_WPE, true>), g, t, 0, st, P, T, Rf, G);
+            else hipLaunchKernelGGL((k_pnp_tri_gated<1, true>), g, t, 0, st, P, T, Rf, G);
+        } else {
+            if (two) hipLaunchKernelGGL((k_pnp_tri_gated<VO_PNP_WPE, false>), g, t, 0, st, P, T, Rf, G);
+            else hipLaunchKernelGGL((k_pnp_tri_gated<1, false>), g, t, 0, st, P, T, Rf, G);
+        }
+        return hip_rc();
+    }
     if (refine_iters > 0) {
         RefArgs Rf = {refine_iters, refine_ftol, refine_info};
         if (two) hipLaunchKernelGGL(k_pnp_tri_ref<VO_PNP_WPE>, dim3(d->B), dim3(256), 0, VO_STREAM(stream), P, T, Rf);
@@ -1699,13 +1901,26 @@ static int launch_pnp_tri(const vo_dims* d, const vo_opts* o, const vo_state* s,
 extern "C" int vo_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
                                      double refine_ftol, double* refine_info, vo_stream_t stream)
 {
-    return launch_pnp_tri(d, o, s, 0, refine_iters, refine_ftol, refine_info, stream);
+    return launch_pnp_tri(d, o, s, 0, refine_iters, refine_ftol, refine_info, nullptr, stream);
+}
+
+extern "C" int vo_pnp_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                                        double refine_ftol, double* refine_info, const vo_tri_opts* tri, vo_stream_t stream)
+{
+    return launch_pnp_tri(d, o, s, 0, refine_iters, refine_ftol, refine_info, tri, stream);
+}
+
+extern "C" int vo_filter_pnp_triangulate_gated(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
+                                               double refine_ftol, double* refine_info, const vo_tri_opts* tri,
+                                               vo_stream_t stream)
+{
+    return launch_pnp_tri(d, o, s, 1, refine_iters, refine_ftol, refine_info, tri, stream);
 }
 
 extern "C" int vo_filter_pnp_triangulate_ex(const vo_dims* d, const vo_opts* o, const vo_state* s, int32_t refine_iters,
                                             double refine_ftol, double* refine_info, vo_stream_t stream)
 {
-    return launch_pnp_tri(d, o, s, 1, refine_iters, refine_ftol, refine_info, stream);
+    return launch_pnp_tri(d, o, s, 1, refine_iters, refine_ftol, refine_info, nullptr, stream);
 }
 
 extern "C" int vo_pnp_triangulate(const vo_dims* d, const vo_opts* o, const vo_state* s, vo_stream_t stream)
@@ -1738,6 +1953,16 @@ extern "C" int vo_triangulate_points(int n, const double* P1, const double* P2, 
     if (n < 0 || (n > 0 && (!P1 || !P2 || !x1 || !x2 || !out4))) return VO_EARG;
     if (n == 0) return VO_OK;
     hipLaunchKernelGGL(k_tri_points, dim3((n + 127) / 128), dim3(128), 0, VO_STREAM(stream), n, P1, P2, x1, x2, out4);
+    return hip_rc();
+}
+
+extern "C" int vo_triangulate_points_err(int n, const double* P1, const double* P2, const float* x1, const float* x2,
+                                         float* out4, double* err2, vo_stream_t stream)
+{
+    if (n < 0 || (n > 0 && (!P1 || !P2 || !x1 || !x2 || !out4 || !err2))) return VO_EARG;
+    if (n == 0) return VO_OK;
+    hipLaunchKernelGGL(k_tri_points_err, dim3((n + 127) / 128), dim3(128), 0, VO_STREAM(stream), n, P1, P2, x1, x2, out4,
+                       err2);
     return hip_rc();
 }
 

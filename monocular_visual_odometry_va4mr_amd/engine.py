@@ -123,6 +123,18 @@ def parse_refine(options: dict) -> tuple[int, float]:
     return int(it), float(ftol)
 
 
+def parse_tri_gate(options: dict):
+    """tri_max_reproj_error of an options dict, validated like lk_fb_threshold: None (absent /
+    None = off) or a positive finite number of pixels."""
+    v = options.get("tri_max_reproj_error")
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+            not (v > 0 and math.isfinite(v)):
+        raise ValueError("tri_max_reproj_error must be a positive finite number of pixels (or None)")
+    return float(v)
+
+
 SUBPIX_MAX_HALF_WIN = 7
 
 
@@ -264,6 +276,15 @@ class Engine:
         # refined to sub-pixel positions by vo_gftt_subpix before feature adding reads them (DESIGN
         # 5e); feature_subpix_iters, feature_subpix_eps, feature_subpix_zero_zone.  No buffer of its own.
         self.feature_subpix = parse_subpix(options)
+        # tri_max_reproj_error (pixels; this build's own key, absent / None = off): a candidate that
+        # passed triangulation's depth gate becomes a landmark only if its point reprojects within
+        # that distance of both observations it was made from, and is dropped otherwise.
+        # The step then goes through the _gated entry points and their kernels.
+        self.tri_max_reproj_error = parse_tri_gate(options)
+        self._tri_info = self._tri_opts = None
+        if self.tri_max_reproj_error is not None:
+            self._tri_info = z(B, 4, dt=torch.int32)
+            self._tri_opts = L.VoTriOpts(self.tri_max_reproj_error, self._tri_info.data_ptr())
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -291,6 +312,15 @@ class Engine:
         if self._refine_info is None:
             return None
         return self._refine_info.cpu().numpy()
+
+    def tri_gate_info(self):
+        """[B][4] int32 of the last step's triangulation under tri_max_reproj_error: candidates that
+        reached cv2.triangulatePoints, kept by the depth gate, dropped by the reprojection gate,
+        appended as landmarks (zeros for a chain that did not triangulate; a chain whose status is
+        set keeps its last row), or None with the option off (no buffer exists then).  Synchronises."""
+        if self._tri_info is None:
+            return None
+        return self._tri_info.cpu().numpy()
 
     def _sw_alloc(self):
         if getattr(self, "_sw_host", None) is None:
@@ -493,7 +523,19 @@ class Engine:
             lat = self._latency_stream()
             lat.wait_stream(main)                                 # tracking done
         sl = C.c_void_p(lat.cuda_stream)
-        if self.pnp_refine_iters:
+        if self._tri_opts is not None:
+            # the same launches through the _gated entry points (with or without the refinement)
+            rit, rtol = self.pnp_refine_iters, C.c_double(self.pnp_refine_ftol)
+            rinfo = C.c_void_p(self._refine_info.data_ptr()) if rit else None
+            tg = C.byref(self._tri_opts)
+            if fused:
+                pnp = lib.vo_filter_pnp_triangulate_gated if defer else lib.vo_pnp_triangulate_gated
+                run(2, lat, lambda: pnp(pd, po, ps, rit, rtol, rinfo, tg, sl))
+                run(3, lat, lambda: 0)
+            else:
+                run(2, lat, lambda: lib.vo_pnp_gated(pd, po, ps, rit, rtol, rinfo, tg, sl))
+                run(3, lat, lambda: lib.vo_triangulate_gated(pd, po, ps, 0, tg, sl))
+        elif self.pnp_refine_iters:
             # the same launches through the _ex entry points, the pose refined inside them
             rit, rtol = self.pnp_refine_iters, C.c_double(self.pnp_refine_ftol)
             rinfo = C.c_void_p(self._refine_info.data_ptr())

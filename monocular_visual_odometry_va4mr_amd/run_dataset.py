@@ -57,14 +57,16 @@ def dataset_frames(dataset: str, path: str):
 def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str | None = "out/interface_plot.png",
         plot_every: int = 0, poses_out: str | None = None, device=None, verbose: bool = False, K=None,
         lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
-        pnp_refine_ftol: float | None = None, feature_subpix_win=None) -> dict:
+        pnp_refine_ftol: float | None = None, feature_subpix_win=None,
+        tri_max_reproj_error: float | None = None) -> dict:
     """Run main.py's loop; returns a summary dict and (in "_vo") the pipeline object.
     K overrides the dataset's intrinsics (e.g. for a synthetic sequence written to disk).
     ``lk_fb_threshold`` (pixels): the engine's forward-backward gate on tracked points; None
     (the reference's behaviour) leaves it off.  ``pnp_refine_iters`` / ``pnp_refine_ftol``: the
     engine's Levenberg-Marquardt refinement of every PnP pose (None or 0 = off).
     ``feature_subpix_win``: half-window of the sub-pixel refinement of the corners feature adding
-    takes (None = off)."""
+    takes (None = off).  ``tri_max_reproj_error`` (pixels): the engine's reprojection-error gate on
+    new landmarks (None = off)."""
     import torch
 
     from .VisualOdometryPipeLine import VisualOdometryPipeLine
@@ -78,6 +80,8 @@ def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str
         options["pnp_refine_ftol"] = pnp_refine_ftol
     if feature_subpix_win is not None:      # sub-pixel refinement of the added corners (half-window); None = off
         options["feature_subpix_win"] = feature_subpix_win
+    if tri_max_reproj_error is not None:    # reprojection gate on triangulated candidates (pixels); None = off
+        options["tri_max_reproj_error"] = tri_max_reproj_error
     last = int(last_frame if last_frame is not None else ref_last)
     dev = torch.device(device or "cuda")
     if dataset.startswith("synthetic-"):
@@ -162,12 +166,15 @@ def main():
                     help="relative cost tolerance of that refinement (default 1e-10)")
     ap.add_argument("--feature-subpix-win", type=int, default=None, metavar="N",
                     help="refine the corners feature adding takes to sub-pixel positions, half-window N (1..7)")
+    ap.add_argument("--tri-max-reproj-error", type=float, default=None, metavar="PX",
+                    help="drop a triangulated candidate whose point reprojects more than PX pixels from either observation")
     a = ap.parse_args()
     if not a.dataset.startswith("synthetic-") and not a.path:
         ap.error("--path is required for a dataset on disk")
     res = run(a.dataset, a.path, a.last_frame, a.plot or None, a.plot_every, a.poses, verbose=a.verbose,
               lk_fb_threshold=a.lk_fb_threshold, pnp_refine_iters=a.pnp_refine_iters,
-              pnp_refine_ftol=a.pnp_refine_ftol, feature_subpix_win=a.feature_subpix_win)
+              pnp_refine_ftol=a.pnp_refine_ftol, feature_subpix_win=a.feature_subpix_win,
+              tri_max_reproj_error=a.tri_max_reproj_error)
     print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
 
 

@@ -55,7 +55,8 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         rank: int = 0, world: int = 1, out_path: str | None = None, engine_cls=None, renderer=None,
         reference: dict | None = None, prerender: bool = True, time_boot: bool = True,
         groups: int | None = None, lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
-        pnp_refine_ftol: float | None = None, feature_subpix_win=None) -> dict | None:
+        pnp_refine_ftol: float | None = None, feature_subpix_win=None,
+        tri_max_reproj_error: float | None = None) -> dict | None:
     """Run the plan; rank 0 returns the report (None on other ranks).
 
     ``engine_cls`` / ``renderer`` default to engine.Engine and synth.Renderer (tests pass
@@ -89,6 +90,8 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         opts["pnp_refine_ftol"] = pnp_refine_ftol
     if feature_subpix_win is not None:      # sub-pixel refinement of the added corners (half-window); None = off
         opts["feature_subpix_win"] = feature_subpix_win
+    if tri_max_reproj_error is not None:    # reprojection gate on triangulated candidates (pixels); None = off
+        opts["tri_max_reproj_error"] = tri_max_reproj_error
     gap = b1 - b0
     plan = Sh.plan_shards(n_frames, world * shards_per_rank, gap, overlap)
     mine = Sh.rank_shards(plan, rank, world)
@@ -357,6 +360,8 @@ def main():
                     help="relative cost tolerance of that refinement (default 1e-10)")
     ap.add_argument("--feature-subpix-win", type=int, default=None, metavar="N",
                     help="refine the corners feature adding takes to sub-pixel positions, half-window N (1..7)")
+    ap.add_argument("--tri-max-reproj-error", type=float, default=None, metavar="PX",
+                    help="drop a triangulated candidate whose point reprojects more than PX pixels from either observation")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -369,7 +374,8 @@ def main():
     ref = reference_shards(args.reference, world * args.shards_per_gpu) if args.reference else None
     res = run(args.preset, args.frames, args.shards_per_gpu, args.overlap, args.seed, dev, rank, world, args.out,
               reference=ref, lk_fb_threshold=args.lk_fb_threshold, pnp_refine_iters=args.pnp_refine_iters,
-              pnp_refine_ftol=args.pnp_refine_ftol, feature_subpix_win=args.feature_subpix_win)
+              pnp_refine_ftol=args.pnp_refine_ftol, feature_subpix_win=args.feature_subpix_win,
+              tri_max_reproj_error=args.tri_max_reproj_error)
     if res is not None:
         print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
     if world > 1:

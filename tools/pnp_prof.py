@@ -2,7 +2,7 @@
 """Phase times of the fused PnP + triangulation launch (k_pnp_tri, block 0) for one KITTI chain
 stepped like the drop-in class (one chain, eager).  Needs the diagnostics build
 (make -C monocular_visual_odometry_va4mr_amd/csrc ../_build/libvo_hip_pnpprof.so).
-usage: python tools/pnp_prof.py [n_frames] [pnp_refine_iters] [chains]
+usage: python tools/pnp_prof.py [n_frames] [pnp_refine_iters] [chains] [tri_max_reproj_error]
 (chains > 1: that many copies of the chain in one engine, e.g. 384 for one group of the headline
 shape; the timestamps are block 0's)"""
 import ctypes as C
@@ -24,6 +24,7 @@ from monocular_visual_odometry_va4mr_amd.synth import Renderer  # noqa: E402
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 refine = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 B = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+tri_gate = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0
 dev = torch.device("cuda")
 opts, (b0, b1), _ = Op.get("kitti")
 gap = b1 - b0
@@ -32,6 +33,8 @@ gt = bench.StagePoses(n + gap + 8, rend.p)
 fr = bench.render_windows(rend, gt, [0], gap, n - 2, dev)[:, 0]
 if refine:
     opts = dict(opts, pnp_refine_iters=refine)
+if tri_gate:
+    opts = dict(opts, tri_max_reproj_error=tri_gate)
 eng = Engine(rend.K, opts, fr.shape[-1], fr.shape[-2], batch=B, device=dev, ncap=16384 if B == 1 else 4096,
              pcap=16384 if B == 1 else 8192, fcap=n + 8)
 eng.bootstrap(fr[0:1].expand(B, -1, -1), fr[1:2].expand(B, -1, -1))
@@ -55,6 +58,8 @@ for i in range(2, n):
         print(f"step {i}: " + " | ".join(f"{k} {v:6.1f}" for k, v in row.items()) +
               f" | hyps {t[20]} niters {t[21]} best {t[22]} | nL {int(eng.t['nL'][0])} nC {int(eng.t['nC'][0])}",
               flush=True)
+if tri_gate:
+    print("triangulation counters (chain 0, last step; reached, depth-kept, dropped, appended):", eng.tri_gate_info()[0].tolist())
 if refine:
     print("refine info (chain 0, last step):", eng.refine_info()[0].tolist())
 print("median us: " + " | ".join(f"{k} {np.median(v[5:]):6.1f}" for k, v in acc.items()), flush=True)

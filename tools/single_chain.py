@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One chain through the drop-in class on KITTI-size frames (for rocprofv3 of the B=1 step).
-usage: python tools/single_chain.py [n_frames] [graph 0/1] [pnp_refine_iters] [feature_subpix_win]"""
+usage: python tools/single_chain.py [n_frames] [graph 0/1] [pnp_refine_iters] [feature_subpix_win] [tri_max_reproj_error]"""
 import os
 import sys
 import time
@@ -23,6 +23,8 @@ if len(sys.argv) > 3 and int(sys.argv[3]):
     opts = dict(opts, pnp_refine_iters=int(sys.argv[3]))
 if len(sys.argv) > 4 and int(sys.argv[4]):
     opts = dict(opts, feature_subpix_win=int(sys.argv[4]))
+if len(sys.argv) > 5 and float(sys.argv[5]):
+    opts = dict(opts, tri_max_reproj_error=float(sys.argv[5]))
 vo = VisualOdometryPipeLine(rend.K, opts, max_frames=n + 8, use_graph=use_graph)
 vo.initialization(fr[boot[0]], fr[boot[1]])
 torch.cuda.synchronize()
