@@ -289,6 +289,35 @@ int vo_lk_points_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int p
 int vo_track_fb(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, double fb_threshold,
                 float* scratch, int compact, vo_stream_t stream);
 
+/* Constant-velocity seeds for the landmark tracks (engine option lk_motion_model; the project's own
+ * definition, DESIGN 5h and the NumPy restatement tests/test_lk_seed_ref.py, reproduced bit for
+ * bit).  No reference counterpart: the reference starts every search at the old pixel (nextPts =
+ * None, :281).  With A = pose slot nF - 2 and B = pose slot nF - 1 (X_world = R X_cam + t), the next
+ * pose is predicted as B (A^-1 B) and every landmark is projected through it with vo_opts.K, all in
+ * fp64 with one rounding per operation.  The projection is the seed iff its depth is > 0, both
+ * coordinates are finite and, as float32, inside [0, W) x [0, H); otherwise the seed is the
+ * landmark's own lm_kp.  Candidates are never seeded.
+ *   seeds: [B][ncap + pcap][2], laid out like trk_pts: rows [0, nL) the landmark seeds, rows
+ * [nL, nL + nC) the candidates' own c_kp, rows past nL + nC not written.  A chain whose status is
+ * not 0 writes nothing; a chain with status 0 and nF < 3 writes its own positions everywhere (with
+ * nF == 2 the two poses are the identity and the bootstrap pose, which are not one frame apart).
+ *   info: [B][4] int32 or NULL: landmarks seen, seeded, fallen back on the depth or a non-finite
+ * value, fallen back on the image bounds (rows of chains whose status is not 0 are not written).
+ * NULL d, o, s or seeds: VO_EARG with nothing launched.  Asynchronous, no host read-back,
+ * capturable into a graph. */
+int vo_predict_seeds(const vo_dims* d, const vo_opts* o, const vo_state* s, float* seeds, int32_t* info,
+                     vo_stream_t stream);
+
+/* Tracking with the forward pass started at seeds (VO_LK_USE_INITIAL_FLOW over the state's points;
+ * seeds as vo_predict_seeds lays them out, read for every tracked row).  fb_threshold == 0: vo_track
+ * (compact = 1) or vo_track_lk (compact = 0); fb_threshold > 0: vo_track_fb with that threshold and
+ * fb_scratch as its scratch, the backward pass unseeded (flags 0) as vo_lk_points_fb defines it.
+ * trk_err is not written in either case (the seeded step runs no L1-error pass).  NULL seeds, a
+ * negative, NaN or infinite threshold, a positive threshold with NULL fb_scratch, or a window
+ * outside vo_lk_points' sizes: VO_EARG with nothing written. */
+int vo_track_seeded(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* seeds,
+                    double fb_threshold, float* fb_scratch, int compact, vo_stream_t stream);
+
 /* cv2.solvePnPRansac(..., SOLVEPNP_P3P) (:343) on [B][cap] points with counts.
  * out: rvec[B][3], tvec[B][3], success[B], inlier mask [B][cap] (u8), n_inl[B]. */
 int vo_pnp_ransac(const vo_opts* o, int B, const float* obj, const float* img,

@@ -28,9 +28,11 @@ within that distance of where it started (vo_track_fb), ``pnp_refine_
 (absent, None or 0 = off; ``pnp_refine_ftol``), which refines every PnP pose by Levenberg-Marquardt
 on the inliers' reprojection error, ``feature_subpix_win`` (half-window; absent or
 None = off; ``feature_subpix_iters``, ``feature_subpix_eps``, ``feature_subpix_zero_zone``), which
-refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix), and
+refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix),
 ``tri_max_reproj_error`` (pixels; absent or None = off), which drops a triangulated candidate whose
-new landmark reprojects further than that from either of its two observations.
+new landmark reprojects further than that from either of its two observations, and
+``lk_motion_model`` (absent or None = off; "constant_velocity"), which starts every landmark's LK
+search at its projection through the pose predicted from the last two.
 """
 from __future__ import annotations
 

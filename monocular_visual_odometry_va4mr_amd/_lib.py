@@ -163,6 +163,8 @@ def _declare(L):
         "vo_lk_points_ex": ([D, O, S, C.c_int, P, P, P, i32, i32, P, P, P, P], C.c_int),
         "vo_lk_points_fb": ([D, O, S, C.c_int, P, P, P, i32, i32, f64, P, P, P, P, P], C.c_int),
         "vo_track_fb": ([D, O, S, C.c_int, f64, P, C.c_int, P], C.c_int),
+        "vo_predict_seeds": ([D, O, S, P, P, P], C.c_int),
+        "vo_track_seeded": ([D, O, S, C.c_int, P, f64, P, C.c_int, P], C.c_int),
         "vo_pnp_ransac": ([O, C.c_int, P, P, P, i32, P, P, P, P, P, P, i64, P], C.c_int),
         "vo_pnp_refine": ([O, C.c_int, P, P, P, P, i32, P, i32, f64, P, P, P, P], C.c_int),
         "vo_pnp_ex": ([D, O, S, i32, f64, P, P], C.c_int),

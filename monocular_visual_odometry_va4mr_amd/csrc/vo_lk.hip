@@ -1115,6 +1115,30 @@ extern "C" int vo_track_fb(const vo_dims* d, const vo_opts* o, const vo_state* s
     return hip_ok() ? VO_OK : VO_EHIP;
 }
 
+// vo_track / vo_track_lk / vo_track_fb with the forward pass started at `seeds` (vo_predict_seeds):
+// the EX instantiations with LKParams::init, no err buffer (so no L1-error pass), then the gate's
+// backward pass, which launch_lk_back leaves unseeded
+extern "C" int vo_track_seeded(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* seeds,
+                               double fb_threshold, float* fb_scratch, int compact, vo_stream_t stream)
+{
+    if (!d || !o || !s || prev < 0 || prev > 1 || !seeds) return VO_EARG;
+    const bool fb = !(fb_threshold == 0.);          // NaN: a threshold, and a bad one
+    if (fb && (!lk_thr_ok(fb_threshold) || !fb_scratch)) return VO_EARG;
+    LKParams P;
+    fill_lk(P, d, o, s, prev);
+    lk_state_segments(P, d, s, nullptr);
+    P.init = seeds;
+    int rc = launch_lk_t<true>(P, d->B, VO_STREAM(stream));
+    if (rc) return rc;
+    if (fb) {
+        rc = launch_lk_back(P, d, o, s, prev, fb_threshold, fb_scratch, VO_STREAM(stream));
+        if (rc) return rc;
+    }
+    if (!compact) return VO_OK;
+    hipLaunchKernelGGL(k_track_compact, dim3(d->B), dim3(256), 0, VO_STREAM(stream), *d, *s);
+    return hip_ok() ? VO_OK : VO_EHIP;
+}
+
 extern "C" int vo_track_lk(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, vo_stream_t stream)
 {
     if (!d || !o || !s || prev < 0 || prev > 1) return VO_EARG;

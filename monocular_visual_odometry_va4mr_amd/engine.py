@@ -16,7 +16,8 @@ The reference's per-frame control flow maps to stages as
                                    feature_subpix_win] + vo_add_corners_finish (also :371-373)
 
 (by default the filtering of feature_tracking, PnP and triangulation run as one launch:
-vo_track_lk + vo_filter_pnp_triangulate; VO_PNP_TRI_SPLIT=1 selects the separate calls)
+vo_track_lk + vo_filter_pnp_triangulate; VO_PNP_TRI_SPLIT=1 selects the separate calls; with the
+option lk_motion_model tracking is vo_predict_seeds + vo_track_seeded)
 
 and runtime ValueErrors of the reference become per-chain status codes (``statuses``).
 """
@@ -133,6 +134,20 @@ def parse_tri_gate(options: dict):
             not (v > 0 and math.isfinite(v)):
         raise ValueError("tri_max_reproj_error must be a positive finite number of pixels (or None)")
     return float(v)
+
+
+MOTION_MODELS = ("constant_velocity",)
+
+
+def parse_motion_model(options: dict):
+    """lk_motion_model of an options dict, validated: None (absent / None = off) or
+    "constant_velocity"."""
+    v = options.get("lk_motion_model")
+    if v is None:
+        return None
+    if not isinstance(v, str) or v not in MOTION_MODELS:
+        raise ValueError('lk_motion_model must be "constant_velocity" (or None)')
+    return v
 
 
 SUBPIX_MAX_HALF_WIN = 7
@@ -285,6 +300,15 @@ class Engine:
         if self.tri_max_reproj_error is not None:
             self._tri_info = z(B, 4, dt=torch.int32)
             self._tri_opts = L.VoTriOpts(self.tri_max_reproj_error, self._tri_info.data_ptr())
+        # lk_motion_model (this build's own key, absent / None = off): "constant_velocity" starts every
+        # landmark's LK search at its projection through the pose predicted from the last two
+        # (vo_predict_seeds), and tracking goes through vo_track_seeded.  The seeds are an
+        # argument of those calls, not a state field.
+        self.lk_motion_model = parse_motion_model(options)
+        self._seeds = self._seed_info = None
+        if self.lk_motion_model is not None:
+            self._seeds = z(B, ncap + pcap, 2, dt=torch.float32)
+            self._seed_info = z(B, 4, dt=torch.int32)
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -321,6 +345,15 @@ class Engine:
         if self._tri_info is None:
             return None
         return self._tri_info.cpu().numpy()
+
+    def seed_info(self):
+        """[B][4] int32 of the last step's seeding under lk_motion_model: landmarks seen, seeded,
+        fallen back on the depth or a non-finite value, fallen back on the image bounds (a chain
+        whose status is set keeps its last row), or None with the option off (no buffer exists
+        then).  Synchronises."""
+        if self._seed_info is None:
+            return None
+        return self._seed_info.cpu().numpy()
 
     def _sw_alloc(self):
         if getattr(self, "_sw_host", None) is None:
@@ -484,6 +517,16 @@ class Engine:
 
             def track(pd, po, ps, prev, strm):
                 return lib.vo_track_fb(pd, po, ps, prev, fb_thr, fb_scr, compact, strm)
+        if self.lk_motion_model is not None:
+            # the seeds, then the same tracking started from them, on the stream that tracks
+            sd, si = C.c_void_p(self._seeds.data_ptr()), C.c_void_p(self._seed_info.data_ptr())
+            sd_thr = C.c_double(self.lk_fb_threshold or 0.0)
+            sd_scr = None if self._fb_scratch is None else C.c_void_p(self._fb_scratch.data_ptr())
+            sd_compact = 0 if defer else 1
+
+            def track(pd, po, ps, prev, strm):
+                rc = lib.vo_predict_seeds(pd, po, ps, sd, si, strm)
+                return rc if rc != 0 else lib.vo_track_seeded(pd, po, ps, prev, sd, sd_thr, sd_scr, sd_compact, strm)
         ts = getattr(self, "track_stream", None)
         if ts is not None and forked and not gftt_late:
             # tracking on a stream shared by the engines of a batch (track_stream): their LK

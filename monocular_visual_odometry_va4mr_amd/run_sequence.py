@@ -56,7 +56,7 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         reference: dict | None = None, prerender: bool = True, time_boot: bool = True,
         groups: int | None = None, lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
         pnp_refine_ftol: float | None = None, feature_subpix_win=None,
-        tri_max_reproj_error: float | None = None) -> dict | None:
+        tri_max_reproj_error: float | None = None, lk_motion_model: str | None = None) -> dict | None:
     """Run the plan; rank 0 returns the report (None on other ranks).
 
     ``engine_cls`` / ``renderer`` default to engine.Engine and synth.Renderer (tests pass
@@ -92,6 +92,8 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         opts["feature_subpix_win"] = feature_subpix_win
     if tri_max_reproj_error is not None:    # reprojection gate on triangulated candidates (pixels); None = off
         opts["tri_max_reproj_error"] = tri_max_reproj_error
+    if lk_motion_model is not None:         # start every landmark's LK search at its predicted projection; None = off
+        opts["lk_motion_model"] = lk_motion_model
     gap = b1 - b0
     plan = Sh.plan_shards(n_frames, world * shards_per_rank, gap, overlap)
     mine = Sh.rank_shards(plan, rank, world)
@@ -362,6 +364,8 @@ def main():
                     help="refine the corners feature adding takes to sub-pixel positions, half-window N (1..7)")
     ap.add_argument("--tri-max-reproj-error", type=float, default=None, metavar="PX",
                     help="drop a triangulated candidate whose point reprojects more than PX pixels from either observation")
+    ap.add_argument("--lk-motion-model", default=None, choices=["constant_velocity"],
+                    help="start every landmark's LK search at its projection through the pose predicted from the last two")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -375,7 +379,7 @@ def main():
     res = run(args.preset, args.frames, args.shards_per_gpu, args.overlap, args.seed, dev, rank, world, args.out,
               reference=ref, lk_fb_threshold=args.lk_fb_threshold, pnp_refine_iters=args.pnp_refine_iters,
               pnp_refine_ftol=args.pnp_refine_ftol, feature_subpix_win=args.feature_subpix_win,
-              tri_max_reproj_error=args.tri_max_reproj_error)
+              tri_max_reproj_error=args.tri_max_reproj_error, lk_motion_model=args.lk_motion_model)
     if res is not None:
         print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
     if world > 1:
