@@ -318,6 +318,48 @@ int vo_predict_seeds(const vo_dims* d, const vo_opts* o, const vo_state* s, floa
 int vo_track_seeded(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* seeds,
                     double fb_threshold, float* fb_scratch, int compact, vo_stream_t stream);
 
+/* Lens distortion (engine option dist_coeffs; the project's own definition in OpenCV's
+ * form, restated in NumPy in tests/test_undistort_ref.py and reproduced bit for bit).  No reference
+ * counterpart: the reference only reads rectified frames.  K, new_K and P are host pointers to
+ * row-major 3x3 doubles of the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (finite, fx and fy not
+ * 0); dist is a host pointer to ndist = 0, 4, 5 or 8 doubles in OpenCV's order k1 k2 p1 p2 [k3 [k4 k5
+ * k6]], missing ones 0 (12 or 14 coefficients and a rectification rotation are not supported).
+ * All three calls are asynchronous on the stream, read nothing back and can be captured; on a bad
+ * argument they return VO_EARG with nothing launched and nothing written.
+ *
+ * cv2.initUndistortRectifyMap(K, dist, None, new_K, (W, H), CV_16SC2): for every pixel (u, v) of
+ * the W x H rectified grid, taken through new_K (NULL = K), the distortion model and K, the raw
+ * position (mx, my) in fp64, quantised as rint(32 m) (half to even), clamped to [-2^20, 2^20 - 1]
+ * (a NaN gives -2^20) and stored as map1 [H][W][2] int16 = (iu >> 5, iv >> 5) and map2 [H][W]
+ * uint16 = (iv & 31) * 32 + (iu & 31).  mapd: [H][W][2] double or NULL, (mx, my) before the
+ * quantisation.  W and H in 1..16384. */
+int vo_undistort_map(const double* K, const double* dist, int ndist, const double* new_K, int W, int H,
+                     int16_t* map1, uint16_t* map2, double* mapd, vo_stream_t stream);
+
+/* cv2.remap(src, map1, map2, INTER_LINEAR, borderMode = BORDER_CONSTANT, borderValue = 0) for B
+ * uint8 images through one fixed-point map: image b is read at src + b * src_stride (rows of
+ * src_pitch bytes, sW x sH pixels) and written at dst + b * dst_stride (rows of dst_pitch bytes,
+ * W x H pixels, the map's size).  With (ix, iy) = map1, a = map2 & 31, b = (map2 >> 5) & 31 and S
+ * the source taken as 0 outside it,
+ *   dst = ((32-a)(32-b) S(ix,iy) + a(32-b) S(ix+1,iy) + (32-a)b S(ix,iy+1) + ab S(ix+1,iy+1) + 512) >> 10
+ * in integers, every tap tested on its own.  Only the W bytes of each destination row are written:
+ * row padding and the bytes between images stay, and the source is not written.  VO_EARG: a NULL
+ * pointer, B < 1, a side outside 1..16384, a pitch below its width, a negative stride, a
+ * destination stride below an image's extent with B > 1, a source image of 2 GiB or more, or a
+ * destination that overlaps the source.  Where dst_stride is a multiple of 4 one thread serves
+ * eight images from one read of the map; any other stride is as valid and takes one image per
+ * thread. */
+int vo_remap_u8(int B, const uint8_t* src, int64_t src_stride, int64_t src_pitch, int sW, int sH, uint8_t* dst,
+                int64_t dst_stride, int64_t dst_pitch, int W, int H, const int16_t* map1, const uint16_t* map2,
+                vo_stream_t stream);
+
+/* cv2.undistortPoints(pts, K, dist, None, P) with a fixed number of iterations (1..100; OpenCV's
+ * default criteria give 5) and no epsilon test: pts [n][2] double raw pixels, out [n][2] double the
+ * ideal normalised coordinates (P = NULL) or pixels through P; rows past n are not written; n = 0
+ * launches nothing.  out may be pts. */
+int vo_undistort_points(int n, const double* pts, const double* K, const double* dist, int ndist, const double* P,
+                        int iters, double* out, vo_stream_t stream);
+
 /* cv2.solvePnPRansac(..., SOLVEPNP_P3P) (:343) on [B][cap] points with counts.
  * out: rvec[B][3], tvec[B][3], success[B], inlier mask [B][cap] (u8), n_inl[B]. */
 int vo_pnp_ransac(const vo_opts* o, int B, const float* obj, const float* img,

@@ -30,9 +30,13 @@ on the inliers' reprojection error, ``feature_subpix_win`` (half-win
 None = off; ``feature_subpix_iters``, ``feature_subpix_eps``, ``feature_subpix_zero_zone``), which
 refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix),
 ``tri_max_reproj_error`` (pixels; absent or None = off), which drops a triangulated candidate whose
-new landmark reprojects further than that from either of its two observations, and
+new landmark reprojects further than that from either of its two observations, 
 ``lk_motion_model`` (absent or None = off; "constant_velocity"), which starts every landmark's LK
-search at its projection through the pose predicted from the last two.
+search at its projection through the pose predicted from the last two, and
+``dist_coeffs`` (absent or None = off; 4, 5 or 8 Brown-Conrady coefficients; ``dist_new_camera_matrix``):
+the images given to ``initialization`` and ``continuous_operation`` are then raw frames of that lens
+and are rectified on the GPU before anything reads them; ``K`` and ``potential_frame``
+stay what the caller gave, and the poses are those of the rectified pinhole camera.
 """
 from __future__ import annotations
 

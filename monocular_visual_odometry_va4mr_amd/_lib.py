@@ -165,6 +165,9 @@ def _declare(L):
         "vo_track_fb": ([D, O, S, C.c_int, f64, P, C.c_int, P], C.c_int),
         "vo_predict_seeds": ([D, O, S, P, P, P], C.c_int),
         "vo_track_seeded": ([D, O, S, C.c_int, P, f64, P, C.c_int, P], C.c_int),
+        "vo_undistort_map": ([P, P, C.c_int, P, C.c_int, C.c_int, P, P, P, P], C.c_int),
+        "vo_remap_u8": ([C.c_int, P, i64, i64, C.c_int, C.c_int, P, i64, i64, C.c_int, C.c_int, P, P, P], C.c_int),
+        "vo_undistort_points": ([C.c_int, P, P, P, C.c_int, P, C.c_int, P, P], C.c_int),
         "vo_pnp_ransac": ([O, C.c_int, P, P, P, i32, P, P, P, P, P, P, i64, P], C.c_int),
         "vo_pnp_refine": ([O, C.c_int, P, P, P, P, i32, P, i32, f64, P, P, P, P], C.c_int),
         "vo_pnp_ex": ([D, O, S, i32, f64, P, P], C.c_int),

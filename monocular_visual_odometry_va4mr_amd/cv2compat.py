@@ -10,7 +10,8 @@ Same names, argument meanings, dtypes and output shapes as the OpenCV 4.6 calls 
     recoverPose           :315
 
 and, beyond the reference, cornerSubPix (the call behind goodFeaturesToTrack in most KLT front
-ends) and solvePnPRefineLM, in this project's own arithmetic.
+ends) and solvePnPRefineLM, in this project's own arithmetic, and the four calls of a camera with
+lens distortion: initUndistortRectifyMap, remap, undistort and undistortPoints.
 
 Each call copies numpy inputs to the device, runs the HIP kernels and copies results
 back (the drop-in mode; the device-resident path is engine.Engine).  Installing this
@@ -40,6 +41,11 @@ IMREAD_GRAYSCALE = 0
 OPTFLOW_USE_INITIAL_FLOW = 4
 OPTFLOW_LK_GET_MIN_EIGENVALS = 8
 NORM_L2 = 4
+INTER_NEAREST = 0
+INTER_LINEAR = 1
+BORDER_CONSTANT = 0
+CV_32FC1 = 5
+CV_16SC2 = 11
 
 
 class error(Exception):
@@ -230,6 +236,153 @@ def cornerSubPix(image, corners, winSize, zeroZone, criteria):
     return corners
 
 
+# ---------------------------------------------------------------- lens distortion
+def _camera(K, what):
+    """K as nine C doubles; the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] is required."""
+    a = np.asarray(K, np.float64)
+    if a.shape == (3, 4):                       # a projection matrix: its camera part
+        a = a[:, :3]
+    if a.shape != (3, 3) or not np.all(np.isfinite(a)) or a[0, 1] != 0 or a[1, 0] != 0 or a[2, 0] != 0 or a[2, 1] != 0 \
+            or a[2, 2] != 1 or a[0, 0] == 0 or a[1, 1] == 0:
+        raise error(f"{what} must be a finite 3x3 matrix of the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+    return (C.c_double * 9)(*a.ravel())
+
+
+def _dist(distCoeffs):
+    """(C doubles or None, count) of 4, 5 or 8 coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]]; None or empty = none."""
+    d = np.zeros(0) if distCoeffs is None else np.asarray(distCoeffs, np.float64).ravel()
+    if d.size in (12, 14):
+        raise NotImplementedError("thin-prism and tilted-sensor models (12 or 14 distortion coefficients) are not supported")
+    if d.size not in (0, 4, 5, 8):
+        raise error("distCoeffs must hold 4, 5 or 8 coefficients (or be None)")
+    return ((C.c_double * d.size)(*d) if d.size else None), int(d.size)
+
+
+def _no_rotation(R):
+    if R is not None and np.asarray(R).size and not np.array_equal(np.asarray(R, np.float64), np.eye(3)):
+        raise NotImplementedError("a rectification rotation R other than None or the identity is not supported")
+
+
+def _empty(m):
+    return m is None or np.asarray(m).size == 0
+
+
+def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type):
+    """cv2.initUndistortRectifyMap over vo_undistort_map (the project's own arithmetic).
+    ``size`` is (W, H), each 1..16384.  ``m1type`` CV_16SC2 gives the fixed-point pair (map1 int16
+    (H, W, 2), map2 uint16 (H, W)); CV_32FC1 gives two float32 (H, W) maps, the fp64 positions
+    rounded once.  An empty ``newCameraMatrix`` is ``cameraMatrix``.  4, 5 or 8 coefficients; 12 or 14
+    and a rotation ``R`` other than None or the identity raise NotImplementedError."""
+    _no_rotation(R)
+    if m1type not in (CV_16SC2, CV_32FC1):
+        raise NotImplementedError("m1type must be CV_16SC2 or CV_32FC1")
+    Kc = _camera(cameraMatrix, "cameraMatrix")
+    Kn = None if _empty(newCameraMatrix) else _camera(newCameraMatrix, "newCameraMatrix")
+    dc, nd = _dist(distCoeffs)
+    W, H = (int(v) for v in size)
+    if not (1 <= W <= 16384 and 1 <= H <= 16384):
+        raise error("size must be (W, H) with both in 1..16384")
+    dev = _dev()
+    m1 = torch.empty((H, W, 2), dtype=torch.int16, device=dev)
+    m2 = torch.empty((H, W), dtype=torch.int16, device=dev)
+    md = torch.empty((H, W, 2), dtype=torch.float64, device=dev) if m1type == CV_32FC1 else None
+    L.check(L.lib().vo_undistort_map(Kc, dc, nd, Kn, W, H, _p(m1), _p(m2), None if md is None else _p(md), _stream()),
+            "vo_undistort_map")
+    if md is not None:
+        m = md.cpu().numpy().astype(np.float32)
+        return np.ascontiguousarray(m[..., 0]), np.ascontiguousarray(m[..., 1])
+    return m1.cpu().numpy(), m2.cpu().numpy().view(np.uint16)
+
+
+def _fixed_point_maps(map1, map2):
+    """The fixed-point pair of remap's map arguments: itself, or two float32 maps quantised on the host
+    as vo_undistort_map quantises (rint(32 m), half to even, clamped to [-2^20, 2^20 - 1], NaN -> -2^20)."""
+    a = np.asarray(map1)
+    if a.dtype == np.int16 and a.ndim == 3 and a.shape[2] == 2:
+        b = np.asarray(map2)
+        if b.dtype != np.uint16 or b.shape != a.shape[:2]:
+            raise error("with a CV_16SC2 map1, map2 must be uint16 (CV_16UC1) of the same size")
+        return np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype == np.float32 and a.ndim == 2 and not _empty(map2):
+        b = np.asarray(map2)
+        if b.dtype != np.float32 or b.shape != a.shape:
+            raise error("with a CV_32FC1 map1, map2 must be float32 (CV_32FC1) of the same size")
+
+        def q(m):
+            with np.errstate(all="ignore"):
+                t = np.rint(32.0 * m.astype(np.float64))
+            return np.where(np.isnan(t), -1048576.0, np.clip(t, -1048576.0, 1048575.0)).astype(np.int64)
+        iu, iv = q(a), q(b)
+        return (np.ascontiguousarray(np.stack([iu >> 5, iv >> 5], -1).astype(np.int16)),
+                ((iv & 31) * 32 + (iu & 31)).astype(np.uint16))
+    raise NotImplementedError("maps must be the CV_16SC2 / CV_16UC1 pair or two CV_32FC1 maps")
+
+
+def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
+    """cv2.remap over vo_remap_u8: a uint8 single-channel ``src`` through the fixed-point pair of
+    initUndistortRectifyMap(CV_16SC2), or through two float32 maps (quantised on the host to the same
+    1/32 pixel), with INTER_LINEAR and a constant border of 0; anything else raises
+    NotImplementedError.  The result has the maps' size."""
+    if interpolation != INTER_LINEAR:
+        raise NotImplementedError("only INTER_LINEAR is supported")
+    if borderMode != BORDER_CONSTANT or np.any(np.asarray(borderValue) != 0):
+        raise NotImplementedError("only borderMode=BORDER_CONSTANT with borderValue=0 is supported")
+    a = np.asarray(src)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise NotImplementedError("remap takes a uint8 single-channel image (CV_8UC1)")
+    img = np.ascontiguousarray(a)
+    m1, m2 = _fixed_point_maps(map1, map2)
+    H, W = m2.shape
+    sH, sW = img.shape
+    if not (1 <= W <= 16384 and 1 <= H <= 16384 and 1 <= sW <= 16384 and 1 <= sH <= 16384):
+        raise error("image and map sides must be in 1..16384")
+    dev = _dev()
+    d_src = torch.from_numpy(img).to(dev)
+    d_m1 = torch.from_numpy(m1).to(dev)
+    d_m2 = torch.from_numpy(m2.view(np.int16)).to(dev)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    L.check(L.lib().vo_remap_u8(1, _p(d_src), sW * sH, sW, sW, sH, _p(out), W * H, W, W, H, _p(d_m1), _p(d_m2), _stream()),
+            "vo_remap_u8")
+    res = out.cpu().numpy()
+    if dst is not None:
+        dst[...] = res
+        return dst
+    return res
+
+
+def undistort(src, cameraMatrix, distCoeffs, dst=None, newCameraMatrix=None):
+    """cv2.undistort: remap(src, *initUndistortRectifyMap(K, dist, None, newK, src's size, CV_16SC2),
+    INTER_LINEAR), with the limits of both."""
+    a = np.asarray(src)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise NotImplementedError("undistort takes a uint8 single-channel image (CV_8UC1)")
+    m1, m2 = initUndistortRectifyMap(cameraMatrix, distCoeffs, None, newCameraMatrix, (a.shape[1], a.shape[0]), CV_16SC2)
+    return remap(a, m1, m2, INTER_LINEAR, dst=dst)
+
+
+def undistortPoints(src, cameraMatrix, distCoeffs, R=None, P=None):
+    """cv2.undistortPoints over vo_undistort_points with OpenCV's default of 5 iterations (a fixed
+    count, no epsilon test): ``src`` float32 or float64 of shape (N, 1, 2) or (N, 2) in raw
+    pixels; returns (N, 1, 2) of the same dtype, normalised coordinates, or pixels through ``P``."""
+    _no_rotation(R)
+    p = np.asarray(src)
+    if p.dtype not in (np.float32, np.float64):
+        raise error("undistortPoints: src must be float32 or float64")
+    if not ((p.ndim == 2 and p.shape[1] == 2) or (p.ndim == 3 and p.shape[1:] == (1, 2))):
+        raise error("undistortPoints: src must have shape (N, 2) or (N, 1, 2)")
+    Kc = _camera(cameraMatrix, "cameraMatrix")
+    Pc = None if _empty(P) else _camera(P, "P")
+    dc, nd = _dist(distCoeffs)
+    n = p.shape[0]
+    if n == 0:
+        return np.zeros((0, 1, 2), p.dtype)
+    dev = _dev()
+    d_pts = torch.from_numpy(np.ascontiguousarray(p.reshape(n, 2).astype(np.float64))).to(dev)
+    out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    L.check(L.lib().vo_undistort_points(n, _p(d_pts), Kc, dc, nd, Pc, 5, _p(out), _stream()), "vo_undistort_points")
+    return out.cpu().numpy().astype(p.dtype).reshape(n, 1, 2)
+
+
 # ---------------------------------------------------------------- PnP (:343)
 def solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec=None, tvec=None,
                    useExtrinsicGuess=False, iterationsCount=100, reprojectionError=8.0,
@@ -237,7 +390,8 @@ def solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec=Non
     if flags != SOLVEPNP_P3P or useExtrinsicGuess:
         raise NotImplementedError("the reference uses flags=SOLVEPNP_P3P (:343)")
     if distCoeffs is not None and np.any(np.asarray(distCoeffs) != 0):
-        raise NotImplementedError("non-zero distortion")
+        raise NotImplementedError("non-zero distortion: rectify the image with undistort, or the points with "
+                                  "undistortPoints(..., P=cameraMatrix), and pass distCoeffs=None")
     obj = np.ascontiguousarray(np.asarray(objectPoints, np.float32).reshape(-1, 3))
     img = np.ascontiguousarray(np.asarray(imagePoints, np.float32).reshape(-1, 2))
     n = obj.shape[0]
@@ -277,7 +431,8 @@ def solvePnPRefineLM(objectPoints, imagePoints, cameraMatrix, distCoeffs, rvec, 
     count is the iteration limit (100 without the COUNT bit), its epsilon the relative cost
     tolerance (0 without the EPS bit)."""
     if distCoeffs is not None and np.any(np.asarray(distCoeffs) != 0):
-        raise NotImplementedError("non-zero distortion")
+        raise NotImplementedError("non-zero distortion: rectify the image with undistort, or the points with "
+                                  "undistortPoints(..., P=cameraMatrix), and pass distCoeffs=None")
     obj = np.ascontiguousarray(np.asarray(objectPoints, np.float32).reshape(-1, 3))
     img = np.ascontiguousarray(np.asarray(imagePoints, np.float32).reshape(-1, 2))
     n = obj.shape[0]

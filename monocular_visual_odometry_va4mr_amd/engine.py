@@ -17,7 +17,8 @@ The reference's per-frame control flow maps to stages as
 
 (by default the filtering of feature_tracking, PnP and triangulation run as one launch:
 vo_track_lk + vo_filter_pnp_triangulate; VO_PNP_TRI_SPLIT=1 selects the separate calls; with the
-option lk_motion_model tracking is vo_predict_seeds + vo_track_seeded)
+option lk_motion_model tracking is vo_predict_seeds + vo_track_seeded; with the option dist_coeffs
+the frames are raw and one vo_remap_u8 launch rectifies them before vo_pyr_build reads them)
 
 and runtime ValueErrors of the reference become per-chain status codes (``statuses``).
 """
@@ -150,6 +151,38 @@ def parse_motion_model(options: dict):
     return v
 
 
+def _pinhole_matrix(K, what: str) -> np.ndarray:
+    """K as float64 3x3 of the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (finite, fx and fy not 0)."""
+    try:
+        K = np.array(K, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a 3x3 camera matrix") from None
+    if K.shape != (3, 3) or not np.all(np.isfinite(K)) or K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 \
+            or K[2, 2] != 1 or K[0, 0] == 0 or K[1, 1] == 0:
+        raise ValueError(f"{what} must be a finite 3x3 camera matrix of the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+    return K
+
+
+def parse_dist(options: dict):
+    """None (off), or (coefficients, new camera matrix or None) of an options dict, validated:
+    dist_coeffs a sequence of 4, 5 or 8 finite numbers in OpenCV's order k1 k2 p1 p2 [k3 [k4 k5 k6]]
+    (absent / None = off; all zeros are accepted and still run the remap), dist_new_camera_matrix a
+    3x3 pinhole matrix (absent / None = the camera's own K).  The matrix is validated whether the
+    rectification is on or not."""
+    nk = options.get("dist_new_camera_matrix")
+    if nk is not None:
+        nk = _pinhole_matrix(nk, "dist_new_camera_matrix")
+    d = options.get("dist_coeffs")
+    if d is None:
+        return None
+    if not isinstance(d, (tuple, list, np.ndarray)) or len(d) not in (4, 5, 8) or np.ndim(d) != 1:
+        raise ValueError("dist_coeffs must be a sequence of 4, 5 or 8 numbers k1 k2 p1 p2 [k3 [k4 k5 k6]] (or None)")
+    for v in d:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError("dist_coeffs must hold finite numbers")
+    return tuple(float(v) for v in d), nk
+
+
 SUBPIX_MAX_HALF_WIN = 7
 
 
@@ -205,7 +238,17 @@ class Engine:
         self.K = np.asarray(K, np.float64)
         self.options = dict(options)
         self.B, self.W, self.H = int(batch), int(width), int(height)
-        self.opts = make_opts(self.K, options)
+        # dist_coeffs (this build's own key, absent / None = off): the frames are raw ones of a camera
+        # with these Brown-Conrady coefficients and intrinsics K.  The rectification map is computed
+        # once, below, and every frame set goes through one vo_remap_u8 launch before anything reads it
+        # (_frames).  Every stage then works in the pinhole camera dist_new_camera_matrix
+        # (None = K), which is what make_opts gets; self.K stays the caller's.
+        self.dist = parse_dist(options)
+        self.K_rect = self.K
+        if self.dist is not None:
+            self.K = _pinhole_matrix(self.K, "K (with dist_coeffs)")
+            self.K_rect = self.K if self.dist[1] is None else self.dist[1]
+        self.opts = make_opts(self.K_rect, options)
         d = L.VoDims()
         d.B, d.W, d.H = self.B, self.W, self.H
         win = tuple(int(v) for v in options["winSize"])
@@ -309,6 +352,17 @@ class Engine:
         if self.lk_motion_model is not None:
             self._seeds = z(B, ncap + pcap, 2, dt=torch.float32)
             self._seed_info = z(B, 4, dt=torch.int32)
+        self._map1 = self._map2 = self._rect = None
+        if self.dist is not None:
+            self._map1 = torch.empty((self.H, self.W, 2), dtype=torch.int16, device=dev)
+            self._map2 = torch.empty((self.H, self.W), dtype=torch.int16, device=dev)      # uint16 values
+            dc = (C.c_double * len(self.dist[0]))(*self.dist[0])
+            Kc = (C.c_double * 9)(*self.K.ravel())
+            Kn = None if self.dist[1] is None else (C.c_double * 9)(*self.dist[1].ravel())
+            L.check(self.lib.vo_undistort_map(Kc, dc, len(dc), Kn, self.W, self.H, C.c_void_p(self._map1.data_ptr()),
+                                              C.c_void_p(self._map2.data_ptr()), None, self.stream), "vo_undistort_map")
+            # once per camera: the map is complete before a step on any other stream can read it
+            torch.cuda.current_stream(dev).synchronize()
         self.t = T
         s = L.VoState()
         for name in L._STATE_FIELDS:
@@ -379,7 +433,11 @@ class Engine:
     def build_pyramid(self, frames: torch.Tensor, which: int, deriv: bool = False):
         """Pyramid + Scharr derivatives of `frames` into pyr[which] / der[which] (vo_pyr_build
         always produces both; deriv=True additionally recomputes der[which] by vo_pyr_deriv)."""
-        frames = self._frames(frames)
+        self._build_pyramid(self._frames(frames), which, deriv)
+
+    def _build_pyramid(self, frames: torch.Tensor, which: int, deriv: bool = False):
+        """build_pyramid for frames as the pipeline holds them (what _frames returned: on the device
+        and, with dist_coeffs, rectified)."""
         self._drain_prefetch()
         self._chk(self.lib.vo_pyr_build(self._pd, self._ps, which, C.c_void_p(frames.data_ptr()),
                                         self.W * self.H, self.stream), "vo_pyr_build")
@@ -402,7 +460,30 @@ class Engine:
             frames = frames.unsqueeze(0)
         if frames.dtype != torch.uint8 or tuple(frames.shape) != (self.B, self.H, self.W):
             raise ValueError(f"frames must be uint8 [{self.B},{self.H},{self.W}]")
-        return frames.to(self.device, non_blocking=True).contiguous()
+        frames = frames.to(self.device, non_blocking=True).contiguous()
+        return frames if self.dist is None else self._rectify(frames)
+
+    def _remap(self, raw: torch.Tensor, out: torch.Tensor):
+        """One vo_remap_u8 launch on the current stream: raw [B,H,W] through the camera's map into out."""
+        n = self.W * self.H
+        self._chk(self.lib.vo_remap_u8(self.B, C.c_void_p(raw.data_ptr()), n, self.W, self.W, self.H,
+                                       C.c_void_p(out.data_ptr()), n, self.W, self.W, self.H,
+                                       C.c_void_p(self._map1.data_ptr()), C.c_void_p(self._map2.data_ptr()), self.stream),
+                  "vo_remap_u8")
+
+    def _rectify(self, raw: torch.Tensor) -> torch.Tensor:
+        """The rectified frames of raw device frames (dist_coeffs).  The last result is kept, keyed by
+        the raw tensor's (data_ptr, _version): a step that receives the frames an earlier step was
+        given as next_frames gets the very tensor the prefetched pyramid was built from, so the
+        prefetch's key still matches and the pyramid is not rebuilt.  The raw tensor is held with it,
+        so its address cannot be handed to another tensor while the entry lives."""
+        key = (raw.data_ptr(), raw._version)
+        if self._rect is not None and self._rect[0] == key:
+            return self._rect[2]
+        out = torch.empty_like(raw)
+        self._remap(raw, out)
+        self._rect = (key, raw, out)
+        return out
 
     STAGES = ("pyr_build", "track", "pnp", "triangulate", "gftt", "add_finish")
 
@@ -649,7 +730,11 @@ class Engine:
             frames = frames.unsqueeze(0)
         if frames.dtype != torch.uint8 or tuple(frames.shape) != tuple(buf.shape):
             raise ValueError(f"frames must be uint8 [{self.B},{self.H},{self.W}]")
-        buf.copy_(frames)
+        if self.dist is None:
+            buf.copy_(frames)
+        else:
+            # rectified straight into the graph's bound buffer, on the stream the replay follows on
+            self._remap(frames.to(self.device, non_blocking=True).contiguous(), buf)
         self.replay_step()
 
     # ------------------------------------------------------------------ bootstrap
@@ -749,7 +834,7 @@ class Engine:
         # class report it) -- no host synchronisation inside the bootstrap
         self.t["status"].copy_(torch.where(ovf > 0, torch.full_like(ovf, L.ST_CAPACITY), self.t["status"]))
         self.prev = 0
-        self.build_pyramid(img1, self.prev)
+        self._build_pyramid(img1, self.prev)
         self._boot_debug = {"n0": n0, "n1": n1, "pts0": pts0, "pts1": pts1, "cnt": cnt}
         if own:
             # the caching allocator only reuses the blocks once the queued kernels are done
@@ -760,7 +845,9 @@ class Engine:
     # ------------------------------------------------------------------ state I/O
     def import_chain(self, b: int, *, landmarks, keypoints, cand, cand_first, cand_tau, transforms,
                      num_pts, prev_img):
-        """Load reference-shaped state into chain b (checkpoint restore / test hook)."""
+        """Load reference-shaped state into chain b (checkpoint restore / test hook).  ``prev_img`` is
+        the potential_frame as the pipeline holds it: with dist_coeffs that is the rectified image,
+        and it is not rectified again here."""
         d = self.dims
         T = self.t
         lm = np.asarray(landmarks, np.float32).reshape(-1, 3)
@@ -792,7 +879,7 @@ class Engine:
         full = torch.zeros((self.B, self.H, self.W), dtype=torch.uint8, device=dev)
         full[b] = img
         keep = T["pyr%d" % self.prev].clone(), T["der%d" % self.prev].clone()
-        self.build_pyramid(full, self.prev)
+        self._build_pyramid(full, self.prev)
         mask = torch.zeros(self.B, dtype=torch.bool, device=dev)
         mask[b] = True
         T["pyr%d" % self.prev][~mask] = keep[0][~mask]

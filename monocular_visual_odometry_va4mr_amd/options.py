@@ -66,3 +66,15 @@ def get(name: str):
     """Return (options dict copy, bootstrap pair, reference last_frame)."""
     opts, boot, last = PRESETS[SEQ_TO_OPTIONS.get(name, name)]
     return copy.deepcopy(opts), tuple(boot), last
+
+
+def parse_dist_arg(text: str) -> list:
+    """The drivers' --dist-coeffs: "k1,k2,p1,p2[,k3[,k4,k5,k6]]" as a list of 4, 5 or 8 floats (the
+    engine option dist_coeffs; engine.parse_dist validates the values)."""
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--dist-coeffs takes comma-separated numbers, got {text!r}") from None
+    if len(vals) not in (4, 5, 8):
+        raise ValueError("--dist-coeffs takes 4, 5 or 8 coefficients: k1,k2,p1,p2[,k3[,k4,k5,k6]]")
+    return vals
