@@ -190,12 +190,12 @@ def border_max_mask(img):
     return np.where(m, 255, 0).astype(np.uint8)
 
 
-def seam_mask(img, axis, line, block_size=3):
+def seam_mask(img, axis, line, block_size=3, use_harris=False):
     """(mask, (x, y)): allowed are the strongest interior pixel of column / row `line` that has a
     stronger neighbour, and every pixel below 0.6 of its value.  With SEAM_QUALITY = 0.5 the threshold
     is half that pixel's value; a maximum taken from any other allowed pixel gives 0.3 of it at most."""
     from oracle import _olib as O
-    e = O.eigmap(img, block_size)
+    e = O.eigmap(img, block_size, use_harris)
     H, W = e.shape
     c = e[1:-1, 1:-1]
     nb = np.full_like(c, -np.inf)
