@@ -318,6 +318,34 @@ int vo_predict_seeds(const vo_dims* d, const vo_opts* o, const vo_state* s, floa
 int vo_track_seeded(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* seeds,
                     double fb_threshold, float* fb_scratch, int compact, vo_stream_t stream);
 
+/* Illumination models of the LK tracker (engine option lk_illumination; the project's own
+ * definition, restated in NumPy in tests/test_lk_illum_ref.py and reproduced bit for bit).  No
+ * reference counterpart: the reference assumes brightness constancy.  Inside every iteration the
+ * mismatch J(x + d) - I(x) is freed by least squares of an additive offset (BIAS) or of an offset and
+ * a gain (GAIN_BIAS) of J against I: the tensor and the right-hand side are built from centred
+ * integer window sums (exact), a few fp64 operations in a fixed order and one rounding to float.
+ * Everything after that (minEig and its tests, the update, the stop tests, bit 8's minimum
+ * eigenvalue) is the plain tracker's on those values.  The level-0 L1 error is the raw one. */
+#define VO_LK_ILLUM_BIAS       1
+#define VO_LK_ILLUM_GAIN_BIAS  2
+
+/* vo_lk_points_ex (fb_threshold == 0; back_pts may be NULL) or vo_lk_points_fb (fb_threshold > 0)
+ * under illumination model illum; the gate's backward pass runs under the same model with flags 0.
+ * Every window, 15x15 included, runs the generic per-level kernel.  illum outside {1, 2}, a bad
+ * flag, bit 4 with init NULL, a negative, NaN or infinite threshold, a positive threshold with
+ * back_pts NULL or a window outside vo_lk_points' sizes: VO_EARG with the outputs untouched. */
+int vo_lk_points_illum(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
+                       const float* pts, const float* init, const int32_t* counts, int32_t cap,
+                       int32_t flags, int32_t illum, double fb_threshold, float* back_pts,
+                       float* out_pts, uint8_t* out_status, float* out_err, vo_stream_t stream);
+
+/* vo_track_seeded under illumination model illum; seeds may be NULL (unseeded).  One entry for plain,
+ * seeded, gated and seeded + gated tracking, compacting (compact = 1) or not.  trk_err is not
+ * written.  Bad arguments as vo_track_seeded and vo_lk_points_illum: VO_EARG with nothing written. */
+int vo_track_illum(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, int32_t illum,
+                   const float* seeds, double fb_threshold, float* fb_scratch, int compact,
+                   vo_stream_t stream);
+
 /* Lens distortion (engine option dist_coeffs; the project's own definition in OpenCV's
  * form, restated in NumPy in tests/test_undistort_ref.py and reproduced bit for bit).  No reference
  * counterpart: the reference only reads rectified frames.  K, new_K and P are host pointers to

@@ -32,7 +32,10 @@ refines the corners feature adding takes to sub-pixel positions (vo_gftt_subpix,
 ``tri_max_reproj_error`` (pixels; absent or None = off), which drops a triangulated candidate whose
 new landmark reprojects further than that from either of its two observations, 
 ``lk_motion_model`` (absent or None = off; "constant_velocity"), which starts every landmark's LK
-search at its projection through the pose predicted from the last two, and
+search at its projection through the pose predicted from the last two,
+``lk_illumination`` (absent or None = off; "bias" or "gain_bias"), which frees every LK iteration's
+mismatch of an additive offset, or of an offset and a gain, between the two frames, for cameras
+with auto-exposure (vo_track_illum), and
 ``dist_coeffs`` (absent or None = off; 4, 5 or 8 Brown-Conrady coefficients; ``dist_new_camera_matrix``):
 the images given to ``initialization`` and ``continuous_operation`` are then raw frames of that lens
 and are rectified on the GPU before anything reads them; ``K`` and ``potential_frame``

@@ -18,6 +18,8 @@ VO_MAX_LEVELS = 8
 VO_BORDER = 16
 VO_LK_USE_INITIAL_FLOW = 4
 VO_LK_GET_MIN_EIGENVALS = 8
+VO_LK_ILLUM_BIAS = 1
+VO_LK_ILLUM_GAIN_BIAS = 2
 
 ST_OK = 0
 ST_NOT_ENOUGH_KP = 1
@@ -165,6 +167,8 @@ def _declare(L):
         "vo_track_fb": ([D, O, S, C.c_int, f64, P, C.c_int, P], C.c_int),
         "vo_predict_seeds": ([D, O, S, P, P, P], C.c_int),
         "vo_track_seeded": ([D, O, S, C.c_int, P, f64, P, C.c_int, P], C.c_int),
+        "vo_lk_points_illum": ([D, O, S, C.c_int, P, P, P, i32, i32, i32, f64, P, P, P, P, P], C.c_int),
+        "vo_track_illum": ([D, O, S, C.c_int, i32, P, f64, P, C.c_int, P], C.c_int),
         "vo_undistort_map": ([P, P, C.c_int, P, C.c_int, C.c_int, P, P, P, P], C.c_int),
         "vo_remap_u8": ([C.c_int, P, i64, i64, C.c_int, C.c_int, P, i64, i64, C.c_int, C.c_int, P, P, P], C.c_int),
         "vo_undistort_points": ([C.c_int, P, P, P, C.c_int, P, C.c_int, P, P], C.c_int),

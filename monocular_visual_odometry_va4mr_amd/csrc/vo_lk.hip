@@ -164,13 +164,28 @@ VO_DEV LKTaps lk_taps(int x, int y, int cols, int rows, int pitch)
     return t;
 }
 
+// k_lk's illumination models (ILL): (float)((G - Ca Cb / V) / N), one centred window sum
+// with the gain term taken out (GB, the caller passes it only with V > 0) or not; one multiply, one
+// divide and one subtract in fp64, in that order
+template <bool GB>
+VO_DEV float lk_comp(int64_t G, int64_t Ca, int64_t Cb, int64_t V, int N)
+{
+    double g = (double)G;
+    if (GB) g = g - ((double)Ca * (double)Cb) / (double)V;
+    return (float)(g / (double)N);
+}
+
 // BIG: a window side exceeds VO_BORDER, so a window accepted by the bounds test (ipx >= -win_w,
 // ipx < cols) can reach up to win - VO_BORDER pixels past the stored border.  Those instantiations
 // address every tap through lk_taps (window gather, J staging, level-0 error pass); the others
 // read the materialised border directly.
 // EX: the variants behind cv2's flags and the forward-backward gate (LKParams::init, eig_err, fwd);
 // the default instantiations hold none of that code.
-template <int MAXJ, bool BIG, bool EX = false>
+// ILL: the illumination model, 0 = none, VO_LK_ILLUM_BIAS, VO_LK_ILLUM_GAIN_BIAS: the
+// tensor and the right-hand side with an additive offset (and a gain) of J against I eliminated by
+// least squares.  Extra exact integer window sums, then lk_comp's few fp64 operations; ILL = 0 holds
+// none of that code.
+template <int MAXJ, bool BIG, bool EX = false, int ILL = 0>
 __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
 {
     extern __shared__ uint32_t lk_tile[];
@@ -244,6 +259,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
             int iw11 = (1 << 14) - iw00 - iw01 - iw10;
             int ival[MAXJ], ixv[MAXJ], iyv[MAXJ];
             int a11 = 0, a12 = 0, a22 = 0;
+            int tix = 0, tiy = 0, ti = 0, tii = 0, tiix = 0, tiiy = 0;     // ILL: sums of Ix, Iy, I, I^2, I Ix, I Iy
             const int64_t ib = (int64_t)(ipy + VO_BORDER) * pitch + (ipx + VO_BORDER);
 #pragma unroll
             for (int j = 0; j < MAXJ; ++j) {
@@ -272,10 +288,40 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                 a11 += __mul24(ixv[j], ixv[j]);
                 a12 += __mul24(ixv[j], iyv[j]);
                 a22 += __mul24(iyv[j], iyv[j]);
+                if constexpr (ILL != 0) {       // per lane below 2^31 at MAXJ = 16: 16 * 8160^2
+                    tix += ixv[j];
+                    tiy += iyv[j];
+                    ti += ival[j];
+                    tii += __mul24(ival[j], ival[j]);
+                    tiix += __mul24(ival[j], ixv[j]);
+                    tiiy += __mul24(ival[j], iyv[j]);
+                }
             }
             const int64_t iA11 = wave_sum_split(a11), iA12 = wave_sum_split(a12), iA22 = wave_sum_split(a22);
             const float FLT_SCALE = 1.f / (1 << 20);
-            const float A11 = (float)iA11 * FLT_SCALE, A12 = (float)iA12 * FLT_SCALE, A22 = (float)iA22 * FLT_SCALE;
+            float A11, A12, A22;
+            int64_t SIx = 0, SIy = 0, SI = 0, Cx = 0, Cy = 0, V = 0;
+            bool gb = false;                    // gain_bias with V > 0: the gain term is taken out
+            if constexpr (ILL != 0) {
+                SIx = wave_sum_split(tix); SIy = wave_sum_split(tiy); SI = wave_sum_split(ti);
+                const int64_t SII = wave_sum_split(tii), SIIx = wave_sum_split(tiix), SIIy = wave_sum_split(tiiy);
+                const int64_t Gxx = npx * iA11 - SIx * SIx, Gxy = npx * iA12 - SIx * SIy, Gyy = npx * iA22 - SIy * SIy;
+                Cx = npx * SIIx - SI * SIx;
+                Cy = npx * SIIy - SI * SIy;
+                V = npx * SII - SI * SI;
+                gb = ILL == VO_LK_ILLUM_GAIN_BIAS && V > 0;
+                if (gb) {
+                    A11 = lk_comp<true>(Gxx, Cx, Cx, V, npx) * FLT_SCALE;
+                    A12 = lk_comp<true>(Gxy, Cx, Cy, V, npx) * FLT_SCALE;
+                    A22 = lk_comp<true>(Gyy, Cy, Cy, V, npx) * FLT_SCALE;
+                } else {
+                    A11 = lk_comp<false>(Gxx, 0, 0, 1, npx) * FLT_SCALE;
+                    A12 = lk_comp<false>(Gxy, 0, 0, 1, npx) * FLT_SCALE;
+                    A22 = lk_comp<false>(Gyy, 0, 0, 1, npx) * FLT_SCALE;
+                }
+            } else {
+                A11 = (float)iA11 * FLT_SCALE; A12 = (float)iA12 * FLT_SCALE; A22 = (float)iA22 * FLT_SCALE;
+            }
             float D = A11 * A22 - A12 * A12;
             const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * ww * wh);
             if constexpr (EX) {
@@ -334,6 +380,7 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                 const uint32_t whi = pack_w(iw00, iw01, iw10, w11, 7, 255);
                 const uint32_t* tb = tile + (iny - ty0) * TW + (inx - tx0);
                 int b1 = 0, b2 = 0;
+                int td = 0, tdi = 0;            // ILL: sums of diff and diff I
 #pragma unroll
                 for (int j = 0; j < MAXJ; ++j) {
                     const uint32_t q = tb[toff[j]];
@@ -343,6 +390,10 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                     const int diff = (int)(sum >> 9) - ival[j];
                     b1 += __mul24(diff, ixv[j]);      // |diff| <= 8160, |grad| <= 4080
                     b2 += __mul24(diff, iyv[j]);
+                    if constexpr (ILL != 0) {
+                        td += live[j] ? diff : 0;       // a dead slot's diff is pixel (0, 0)'s; the products
+                        tdi += __mul24(diff, ival[j]);  // need no mask: ival, ixv and iyv are zero there
+                    }
                 }
                 // 32-bit reductions when every partial is below 2^24 (total < 2^30)
                 const bool wide = __ballot((uint32_t)(b1 + (1 << 24)) >= (1u << 25) ||
@@ -350,8 +401,21 @@ __global__ void __launch_bounds__(64) k_lk(LKParams P, int level, int B, int nb)
                 int64_t s1, s2;
                 if (!wide) { s1 = wave_sum_dpp(b1); s2 = wave_sum_dpp(b2); }
                 else { s1 = wave_sum_split(b1); s2 = wave_sum_split(b2); }
-                const float fb1 = (float)s1 * FLT_SCALE;
-                const float fb2 = (float)s2 * FLT_SCALE;
+                float fb1, fb2;
+                if constexpr (ILL != 0) {
+                    const int64_t Sd = wave_sum_split(td), SdI = wave_sum_split(tdi);
+                    const int64_t Bx = npx * s1 - Sd * SIx, By = npx * s2 - Sd * SIy, Cd = npx * SdI - SI * Sd;
+                    if (gb) {
+                        fb1 = lk_comp<true>(Bx, Cd, Cx, V, npx) * FLT_SCALE;
+                        fb2 = lk_comp<true>(By, Cd, Cy, V, npx) * FLT_SCALE;
+                    } else {
+                        fb1 = lk_comp<false>(Bx, 0, 0, 1, npx) * FLT_SCALE;
+                        fb2 = lk_comp<false>(By, 0, 0, 1, npx) * FLT_SCALE;
+                    }
+                } else {
+                    fb1 = (float)s1 * FLT_SCALE;
+                    fb2 = (float)s2 * FLT_SCALE;
+                }
                 const float ddx = (A12 * fb2 - A22 * fb1) * D;
                 const float ddy = (A12 * fb1 - A11 * fb2) * D;
                 nx += ddx;
@@ -987,9 +1051,12 @@ static void fill_lk(LKParams& P, const vo_dims* d, const vo_opts* o, const vo_st
     P.thr2 = 0.;
 }
 
-template <bool EX>
+// ILL (with EX): an illumination model; every window then goes through k_lk, one launch per level
+// (k_lk_w holds no model)
+template <bool EX, int ILL = 0>
 static int launch_lk_t(const LKParams& P, int B, hipStream_t st)
 {
+    static_assert(EX || ILL == 0, "the illumination model lives in the EX instantiations");
     const int npx = P.win_w * P.win_h;
     if (P.win_w <= 2 || P.win_h <= 2 || P.win_w > 32 || P.win_h > 32 || npx > 64 * 16 || B < 1) return VO_EARG;
     // One wave per block (iteration counts differ wildly between points, so a wave's slot
@@ -1004,7 +1071,7 @@ static int launch_lk_t(const LKParams& P, int B, hipStream_t st)
     // the last pyramid level
     const int L = P.L;
     const int64_t pyr_end = P.loff[L] + (int64_t)(P.lh[L] + 2 * VO_BORDER) * P.lpitch[L];
-    const bool staged15 = P.win_w == 15 && P.win_h == 15 && P.pstride >= pyr_end + 64;
+    const bool staged15 = ILL == 0 && P.win_w == 15 && P.win_h == 15 && P.pstride >= pyr_end + 64;
     const size_t lds = 4 * (size_t)(P.win_w + 2 * LK_M) * (P.win_h + 2 * LK_M);
     if (lds > 60 * 1024) return VO_EARG;
     // 15x15 (every reference configuration, main.py:36,66,96): all levels in one launch, each
@@ -1021,21 +1088,37 @@ static int launch_lk_t(const LKParams& P, int B, hipStream_t st)
     // (more than 256 pixels always has such a side)
     const bool big = P.win_w > VO_BORDER || P.win_h > VO_BORDER;
     for (int level = P.L; level >= 0; --level) {
-        if (npx > 256) hipLaunchKernelGGL((k_lk<16, true, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
-        else if (big) hipLaunchKernelGGL((k_lk<4, true, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
-        else hipLaunchKernelGGL((k_lk<4, false, EX>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        if (npx > 256) hipLaunchKernelGGL((k_lk<16, true, EX, ILL>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else if (big) hipLaunchKernelGGL((k_lk<4, true, EX, ILL>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
+        else hipLaunchKernelGGL((k_lk<4, false, EX, ILL>), dim3(nblk), dim3(64), lds, st, P, level, B, nb);
     }
     return hip_ok() ? VO_OK : VO_EHIP;
 }
 
 static int launch_lk(const LKParams& P, int B, hipStream_t st) { return launch_lk_t<false>(P, B, st); }
 
+// the EX launch under illumination model illum (0: none)
+static int launch_lk_illum(const LKParams& P, int B, hipStream_t st, int illum)
+{
+    if (illum == VO_LK_ILLUM_BIAS) return launch_lk_t<true, VO_LK_ILLUM_BIAS>(P, B, st);
+    if (illum == VO_LK_ILLUM_GAIN_BIAS) return launch_lk_t<true, VO_LK_ILLUM_GAIN_BIAS>(P, B, st);
+    return illum == 0 ? launch_lk_t<true>(P, B, st) : VO_EARG;
+}
+
+// the argument test of launch_lk_t alone: entries that launch twice (the gate) ask before the first
+static bool lk_window_ok(const vo_opts* o)
+{
+    const int64_t lds = 4 * (int64_t)(o->win_w + 2 * LK_M) * (o->win_h + 2 * LK_M);
+    return o->win_w > 2 && o->win_h > 2 && o->win_w <= 32 && o->win_h <= 32 && o->win_w * o->win_h <= 64 * 16 &&
+           lds <= 60 * 1024;
+}
+
 // The backward pass of the forward-backward gate for the forward call F (already launched on st):
 // LK with flags 0 from next to prev (fill_lk with the roles swapped gives the other pyramid's
 // derivatives) of F's results where F's status is 1, into `back`; each wave then writes its point's
 // gate over F's status.  F's point segments stay: they give the count and the gate's origin.
 static int launch_lk_back(const LKParams& F, const vo_dims* d, const vo_opts* o, const vo_state* s, int prev,
-                          double thr, float* back, hipStream_t st)
+                          double thr, float* back, hipStream_t st, int illum = 0)
 {
     LKParams P;
     fill_lk(P, d, o, s, 1 - prev);
@@ -1045,7 +1128,7 @@ static int launch_lk_back(const LKParams& F, const vo_dims* d, const vo_opts* o,
     P.out = back; P.st = F.st; P.err = nullptr; P.ocap = F.ocap;
     P.fwd = F.out;
     P.thr2 = thr * thr;
-    return launch_lk_t<true>(P, d->B, st);
+    return launch_lk_illum(P, d->B, st, illum);
 }
 
 static bool lk_thr_ok(double thr) { return thr > 0. && thr <= DBL_MAX; }   // false for NaN too
@@ -1132,6 +1215,56 @@ extern "C" int vo_track_seeded(const vo_dims* d, const vo_opts* o, const vo_stat
     if (rc) return rc;
     if (fb) {
         rc = launch_lk_back(P, d, o, s, prev, fb_threshold, fb_scratch, VO_STREAM(stream));
+        if (rc) return rc;
+    }
+    if (!compact) return VO_OK;
+    hipLaunchKernelGGL(k_track_compact, dim3(d->B), dim3(256), 0, VO_STREAM(stream), *d, *s);
+    return hip_ok() ? VO_OK : VO_EHIP;
+}
+
+extern "C" int vo_lk_points_illum(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, const float* pts,
+                                  const float* init, const int32_t* counts, int32_t cap, int32_t flags, int32_t illum,
+                                  double fb_threshold, float* back_pts, float* out_pts, uint8_t* out_status,
+                                  float* out_err, vo_stream_t stream)
+{
+    if (!d || !o || !s || !pts || !counts || !out_pts || !out_status || prev < 0 || prev > 1) return VO_EARG;
+    if ((flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)) || ((flags & VO_LK_USE_INITIAL_FLOW) && !init))
+        return VO_EARG;
+    if (illum != VO_LK_ILLUM_BIAS && illum != VO_LK_ILLUM_GAIN_BIAS) return VO_EARG;
+    const bool fb = !(fb_threshold == 0.);          // NaN: a threshold, and a bad one
+    if (fb && (!lk_thr_ok(fb_threshold) || !back_pts)) return VO_EARG;
+    if (!lk_window_ok(o) || d->B < 1) return VO_EARG;
+    LKParams P;
+    fill_lk(P, d, o, s, prev);
+    lk_point_segments(P, pts, counts, cap, out_pts, out_status, out_err);
+    P.init = (flags & VO_LK_USE_INITIAL_FLOW) ? init : nullptr;
+    P.eig_err = (flags & VO_LK_GET_MIN_EIGENVALS) != 0;
+    int rc = launch_lk_illum(P, d->B, VO_STREAM(stream), illum);
+    if (rc || !fb) return rc;
+    LKParams F = {};
+    lk_point_segments(F, pts, counts, cap, out_pts, out_status, nullptr);
+    return launch_lk_back(F, d, o, s, prev, fb_threshold, back_pts, VO_STREAM(stream), illum);
+}
+
+// vo_track_seeded under an illumination model, seeded or not: the forward pass, the gate's backward
+// pass under the same model, the compaction
+extern "C" int vo_track_illum(const vo_dims* d, const vo_opts* o, const vo_state* s, int prev, int32_t illum,
+                              const float* seeds, double fb_threshold, float* fb_scratch, int compact,
+                              vo_stream_t stream)
+{
+    if (!d || !o || !s || prev < 0 || prev > 1) return VO_EARG;
+    if (illum != VO_LK_ILLUM_BIAS && illum != VO_LK_ILLUM_GAIN_BIAS) return VO_EARG;
+    const bool fb = !(fb_threshold == 0.);          // NaN: a threshold, and a bad one
+    if (fb && (!lk_thr_ok(fb_threshold) || !fb_scratch)) return VO_EARG;
+    if (!lk_window_ok(o) || d->B < 1) return VO_EARG;
+    LKParams P;
+    fill_lk(P, d, o, s, prev);
+    lk_state_segments(P, d, s, nullptr);
+    P.init = seeds;
+    int rc = launch_lk_illum(P, d->B, VO_STREAM(stream), illum);
+    if (rc) return rc;
+    if (fb) {
+        rc = launch_lk_back(P, d, o, s, prev, fb_threshold, fb_scratch, VO_STREAM(stream), illum);
         if (rc) return rc;
     }
     if (!compact) return VO_OK;

@@ -135,7 +135,7 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, mask=None,
 # ---------------------------------------------------------------- LK (:281,:287)
 def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), maxLevel=3,
                          criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, 30, 0.01), flags=0,
-                         minEigThreshold=1e-4):
+                         minEigThreshold=1e-4, *, illumination=None):
     """cv2.calcOpticalFlowPyrLK.  ``flags``: OPTFLOW_USE_INITIAL_FLOW (each point's estimate starts
     at ``nextPts``, float32 with as many points as ``prevPts``) and OPTFLOW_LK_GET_MIN_EIGENVALS
     (``err`` is the minimum eigenvalue of the level-0 tensor, for every point whose window is in
@@ -145,7 +145,12 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), m
     21x21 included); any other window raises (vo_lk_points_ex returns VO_EARG).  15x15 runs the one-launch kernel k_lk_w, every other size
     the per-level k_lk; sides above the pyramid's 16-pixel border take the window's taps at
     reflect-101 coordinates with zero derivatives outside the image, as OpenCV's winSize-wide
-    pyramid border does."""
+    pyramid border does.  ``illumination`` is a keyword of this project's own (cv2 has none): None
+    (off), "bias" or "gain_bias" frees the mismatch of an additive offset, or of an offset and a
+    gain, of ``nextImg`` against ``prevImg`` (vo_lk_points_illum; every window then runs
+    k_lk); any other value raises ValueError."""
+    from .engine import ILLUMINATION_MODELS, parse_illumination
+    illumination = parse_illumination({"lk_illumination": illumination})
     flags = int(flags)
     if flags & ~(OPTFLOW_USE_INITIAL_FLOW | OPTFLOW_LK_GET_MIN_EIGENVALS):
         raise NotImplementedError("only OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_LK_GET_MIN_EIGENVALS are supported")
@@ -181,8 +186,13 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(21, 21), m
     st = torch.empty((1, n), dtype=torch.uint8, device=dev)
     err = torch.empty((1, n), dtype=torch.float32, device=dev)
     di = None if ini is None else torch.from_numpy(ini).to(dev).reshape(1, n, 2)
-    L.check(eng.lib.vo_lk_points_ex(eng._pd, eng._po, eng._ps, 0, _p(dp), None if di is None else _p(di), _p(cnt), n,
-                                    flags, _p(out), _p(st), _p(err), _stream()), "vo_lk_points_ex")
+    if illumination is not None:
+        L.check(eng.lib.vo_lk_points_illum(eng._pd, eng._po, eng._ps, 0, _p(dp), None if di is None else _p(di), _p(cnt),
+                                           n, flags, ILLUMINATION_MODELS[illumination], C.c_double(0.0), None, _p(out),
+                                           _p(st), _p(err), _stream()), "vo_lk_points_illum")
+    else:
+        L.check(eng.lib.vo_lk_points_ex(eng._pd, eng._po, eng._ps, 0, _p(dp), None if di is None else _p(di), _p(cnt), n,
+                                        flags, _p(out), _p(st), _p(err), _stream()), "vo_lk_points_ex")
     return (out.cpu().numpy().reshape(shape), st.cpu().numpy().reshape(-1, 1),
             err.cpu().numpy().reshape(-1, 1))
 

@@ -17,7 +17,8 @@ The reference's per-frame control flow maps to stages as
 
 (by default the filtering of feature_tracking, PnP and triangulation run as one launch:
 vo_track_lk + vo_filter_pnp_triangulate; VO_PNP_TRI_SPLIT=1 selects the separate calls; with the
-option lk_motion_model tracking is vo_predict_seeds + vo_track_seeded; with the option dist_coeffs
+option lk_motion_model tracking is vo_predict_seeds + vo_track_seeded; with the option
+lk_illumination it is vo_track_illum, behind vo_predict_seeds where both are set; with the option dist_coeffs
 the frames are raw and one vo_remap_u8 launch rectifies them before vo_pyr_build reads them)
 
 and runtime ValueErrors of the reference become per-chain status codes (``statuses``).
@@ -148,6 +149,20 @@ def parse_motion_model(options: dict):
         return None
     if not isinstance(v, str) or v not in MOTION_MODELS:
         raise ValueError('lk_motion_model must be "constant_velocity" (or None)')
+    return v
+
+
+ILLUMINATION_MODELS = {"bias": 1, "gain_bias": 2}      # VO_LK_ILLUM_BIAS, VO_LK_ILLUM_GAIN_BIAS
+
+
+def parse_illumination(options: dict):
+    """lk_illumination of an options dict, validated: None (absent / None = off), "bias" or
+    "gain_bias"."""
+    v = options.get("lk_illumination")
+    if v is None:
+        return None
+    if not isinstance(v, str) or v not in ILLUMINATION_MODELS:
+        raise ValueError('lk_illumination must be "bias" or "gain_bias" (or None)')
     return v
 
 
@@ -352,6 +367,11 @@ class Engine:
         if self.lk_motion_model is not None:
             self._seeds = z(B, ncap + pcap, 2, dt=torch.float32)
             self._seed_info = z(B, 4, dt=torch.int32)
+        # lk_illumination (this build's own key, absent / None = off): "bias" or "gain_bias" frees the
+        # tracker's mismatch of an additive offset, or of an offset and a gain, of the new frame against
+        # the old one inside every LK iteration; tracking goes through vo_track_illum, which
+        # also takes the seeds and the gate of the two options above.  No buffer of its own.
+        self.lk_illumination = parse_illumination(options)
         self._map1 = self._map2 = self._rect = None
         if self.dist is not None:
             self._map1 = torch.empty((self.H, self.W, 2), dtype=torch.int16, device=dev)
@@ -608,6 +628,18 @@ class Engine:
             def track(pd, po, ps, prev, strm):
                 rc = lib.vo_predict_seeds(pd, po, ps, sd, si, strm)
                 return rc if rc != 0 else lib.vo_track_seeded(pd, po, ps, prev, sd, sd_thr, sd_scr, sd_compact, strm)
+        if self.lk_illumination is not None:
+            # one entry for every form above: seeded or not, gated or not, compacting or not
+            il = ILLUMINATION_MODELS[self.lk_illumination]
+            il_sd = None if self._seeds is None else C.c_void_p(self._seeds.data_ptr())
+            il_si = None if self._seed_info is None else C.c_void_p(self._seed_info.data_ptr())
+            il_thr = C.c_double(self.lk_fb_threshold or 0.0)
+            il_scr = None if self._fb_scratch is None else C.c_void_p(self._fb_scratch.data_ptr())
+            il_compact = 0 if defer else 1
+
+            def track(pd, po, ps, prev, strm):
+                rc = 0 if il_sd is None else lib.vo_predict_seeds(pd, po, ps, il_sd, il_si, strm)
+                return rc if rc != 0 else lib.vo_track_illum(pd, po, ps, prev, il, il_sd, il_thr, il_scr, il_compact, strm)
         ts = getattr(self, "track_stream", None)
         if ts is not None and forked and not gftt_late:
             # tracking on a stream shared by the engines of a batch (track_stream): their LK

@@ -59,7 +59,7 @@ def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str
         lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
         pnp_refine_ftol: float | None = None, feature_subpix_win=None,
         tri_max_reproj_error: float | None = None, lk_motion_model: str | None = None,
-        dist_coeffs=None) -> dict:
+        dist_coeffs=None, lk_illumination: str | None = None) -> dict:
     """Run main.py's loop; returns a summary dict and (in "_vo") the pipeline object.
     K overrides the dataset's intrinsics (e.g. for a synthetic sequence written to disk).
     ``lk_fb_threshold`` (pixels): the engine's forward-backward gate on tracked points; None
@@ -70,7 +70,9 @@ def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str
     new landmarks (None = off).  ``lk_motion_model``: "constant_velocity" seeds the landmark tracks
     with a prediction of the next pose (None = off).  ``dist_coeffs``: the camera's distortion
     coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]]; the frames are then raw ones, rectified on the GPU
-    before the pyramid build (None = off: the frames are rectified already)."""
+    before the pyramid build (None = off: the frames are rectified already).  ``lk_illumination``:
+    "bias" or "gain_bias" frees every LK iteration's mismatch of an exposure offset, or of an offset
+    and a gain, between the two frames (None = off)."""
     import torch
 
     from .VisualOdometryPipeLine import VisualOdometryPipeLine
@@ -88,6 +90,8 @@ def run(dataset: str, path: str | None, last_frame: int | None = None, plot: str
         options["tri_max_reproj_error"] = tri_max_reproj_error
     if lk_motion_model is not None:         # start every landmark's LK search at its predicted projection; None = off
         options["lk_motion_model"] = lk_motion_model
+    if lk_illumination is not None:         # free LK's mismatch of an exposure offset ("bias") or offset and gain; None = off
+        options["lk_illumination"] = lk_illumination
     if dist_coeffs is not None:             # raw frames of a camera with these coefficients, rectified on the GPU; None = off
         options["dist_coeffs"] = list(dist_coeffs)
     last = int(last_frame if last_frame is not None else ref_last)
@@ -178,6 +182,8 @@ def main():
                     help="drop a triangulated candidate whose point reprojects more than PX pixels from either observation")
     ap.add_argument("--lk-motion-model", default=None, choices=["constant_velocity"],
                     help="start every landmark's LK search at its projection through the pose predicted from the last two")
+    ap.add_argument("--lk-illumination", default=None, choices=["bias", "gain_bias"],
+                    help="free every LK iteration's mismatch of an additive offset (bias) or of an offset and a gain between the frames")
     ap.add_argument("--dist-coeffs", type=Op.parse_dist_arg, default=None, metavar="k1,k2,p1,p2[,k3[,k4,k5,k6]]",
                     help="the frames are raw: rectify them on the GPU with these distortion coefficients (as --dist-coeffs=-0.28,...)")
     a = ap.parse_args()
@@ -187,7 +193,7 @@ def main():
               lk_fb_threshold=a.lk_fb_threshold, pnp_refine_iters=a.pnp_refine_iters,
               pnp_refine_ftol=a.pnp_refine_ftol, feature_subpix_win=a.feature_subpix_win,
               tri_max_reproj_error=a.tri_max_reproj_error, lk_motion_model=a.lk_motion_model,
-              dist_coeffs=a.dist_coeffs)
+              dist_coeffs=a.dist_coeffs, lk_illumination=a.lk_illumination)
     print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
 
 

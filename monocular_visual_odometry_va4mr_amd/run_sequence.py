@@ -57,7 +57,7 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         groups: int | None = None, lk_fb_threshold: float | None = None, pnp_refine_iters: int | None = None,
         pnp_refine_ftol: float | None = None, feature_subpix_win=None,
         tri_max_reproj_error: float | None = None, lk_motion_model: str | None = None,
-        dist_coeffs=None) -> dict | None:
+        dist_coeffs=None, lk_illumination: str | None = None) -> dict | None:
     """Run the plan; rank 0 returns the report (None on other ranks).
 
     ``engine_cls`` / ``renderer`` default to engine.Engine and synth.Renderer (tests pass
@@ -95,6 +95,8 @@ def run(preset: str, n_frames: int, shards_per_rank: int, overlap: int = 30, see
         opts["tri_max_reproj_error"] = tri_max_reproj_error
     if lk_motion_model is not None:         # start every landmark's LK search at its predicted projection; None = off
         opts["lk_motion_model"] = lk_motion_model
+    if lk_illumination is not None:         # free LK's mismatch of an exposure offset ("bias") or offset and gain; None = off
+        opts["lk_illumination"] = lk_illumination
     if dist_coeffs is not None:             # raw frames of a camera with these coefficients, rectified on the GPU; None = off
         opts["dist_coeffs"] = list(dist_coeffs)
     gap = b1 - b0
@@ -369,6 +371,8 @@ def main():
                     help="drop a triangulated candidate whose point reprojects more than PX pixels from either observation")
     ap.add_argument("--lk-motion-model", default=None, choices=["constant_velocity"],
                     help="start every landmark's LK search at its projection through the pose predicted from the last two")
+    ap.add_argument("--lk-illumination", default=None, choices=["bias", "gain_bias"],
+                    help="free every LK iteration's mismatch of an additive offset (bias) or of an offset and a gain between the frames")
     ap.add_argument("--dist-coeffs", type=Op.parse_dist_arg, default=None, metavar="k1,k2,p1,p2[,k3[,k4,k5,k6]]",
                     help="the frames are raw: rectify them on the GPU with these distortion coefficients (as --dist-coeffs=-0.28,...)")
     args = ap.parse_args()
@@ -385,7 +389,7 @@ def main():
               reference=ref, lk_fb_threshold=args.lk_fb_threshold, pnp_refine_iters=args.pnp_refine_iters,
               pnp_refine_ftol=args.pnp_refine_ftol, feature_subpix_win=args.feature_subpix_win,
               tri_max_reproj_error=args.tri_max_reproj_error, lk_motion_model=args.lk_motion_model,
-              dist_coeffs=args.dist_coeffs)
+              dist_coeffs=args.dist_coeffs, lk_illumination=args.lk_illumination)
     if res is not None:
         print(json.dumps({k: v for k, v in res.items() if not k.startswith("_")}))
     if world > 1:

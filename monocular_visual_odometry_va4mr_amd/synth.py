@@ -285,3 +285,27 @@ def make_sequence(preset: str, n_frames: int, seed: int = 0, start: int = 0, dev
     fr, Rs, cs = r.frames(n_frames, start)
     arr = torch.stack(fr).cpu().numpy()
     return arr, r.K, Rs, cs
+
+
+def apply_exposure(frames, start: int = 0, drift: float = 0.15, period: float = 40.0, step_at: int = 12,
+                   step_gain: float = 1.25, offset_amp: float = 8.0, offset_period: float = 25.0):
+    """An auto-exposure schedule over rendered frames (uint8 [n, H, W], numpy or torch): frame t
+    (global index start + i) becomes clip(rint(g_t * frame + o_t), 0, 255) with
+
+        g_t = (1 + drift * sin(2 pi t / period)) * (step_gain if t >= step_at else 1)
+        o_t = offset_amp * sin(2 pi t / offset_period)
+
+    a slow gain drift of +-15 % over 40 frames, one step change of x1.25 at frame 12 and an offset
+    wandering by +-8 grey levels over 25 frames (the defaults).  Computed in float64, so numpy and
+    torch inputs give the same bytes; returns the input's type.  Returns (frames, g [n], o [n])."""
+    n = len(frames)
+    t = np.arange(start, start + n, dtype=np.float64)
+    g = (1.0 + drift * np.sin(2.0 * np.pi * t / period)) * np.where(t >= step_at, step_gain, 1.0)
+    o = offset_amp * np.sin(2.0 * np.pi * t / offset_period)
+    if isinstance(frames, torch.Tensor):
+        gt = torch.as_tensor(g, device=frames.device).view(-1, 1, 1)
+        ot = torch.as_tensor(o, device=frames.device).view(-1, 1, 1)
+        out = torch.clamp(torch.round(gt * frames.to(torch.float64) + ot), 0, 255).to(torch.uint8)
+    else:
+        out = np.clip(np.rint(g[:, None, None] * np.asarray(frames).astype(np.float64) + o[:, None, None]), 0, 255).astype(np.uint8)
+    return out, g, o
